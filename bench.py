@@ -27,11 +27,22 @@ run B frames per rank with no data-path collective (weak scaling); only the timi
 barrier and a MAX-reduction of the elapsed time cross ranks.  `n_gpus` is the world
 size of the initialised process group.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a
-`roofline` object for the dominant kernel family (backbone convs; by default in
-the split-bf16 fp32 arithmetic, --conv-arith f32 for the exact-f32 MFMA kernels), `roofline_warp` for the IPM warp kernel (HBM-bound), and, at N = 1, a
-`cpu_baseline` (the reference's torch-CPU composition, timed on this host on
-a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run (`--gpus N --steps K --warmup W`)
+does only what the headline figure needs: set-up, W warm-up steps, K timed steps,
+then the line with `metric`, `value` (frames/s), `ms_per_step` (milliseconds per
+timed step), the workload's `config` and the library's `build` digests.
+`--dump-outputs DIR` also writes what the last timed step returned to
+DIR/bev.npy and DIR/feats.npy (float32; see dump_outputs); the inputs and weights
+are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else to that line, as every run did before the option
+existed: HIP events around every conv / warp launch and around both stages inside
+the timed steps, from them a `roofline` object for the dominant kernel family
+(backbone convs; by default in the split-bf16 fp32 arithmetic, --conv-arith f32
+for the exact-f32 MFMA kernels) and `roofline_warp` for the IPM warp kernel
+(HBM-bound), `h2d_inclusive` (further steps with the images copied from pinned
+host memory) and, at N = 1, a `cpu_baseline` and `cpu_k1` (the reference's
+torch-CPU composition, timed on this host on a bounded sample; --cpu-iters).
 """
 from __future__ import annotations
 
@@ -57,6 +68,8 @@ PEAK_F32_MFMA_TF = 157.3  # MI355X fp32 matrix spec (= vector peak)
 PEAK_BF16_MFMA_TF = 2500.0  # MI355X bf16 matrix, dense (MI355X_MICROARCH.md)
 # the split arithmetic spends 6 bf16 partial products per fp32 product: its fp32-equivalent dense peak
 PEAK_X6_TF = PEAK_BF16_MFMA_TF / 6
+DUMP_MAX_ELEMS = 6_000_000  # --dump-outputs: elements written per array (the whole array, or a sample of this size)
+DUMP_SEED = 20240611        # --dump-outputs: seed of the sample's indices
 
 
 def parse():
@@ -77,7 +90,16 @@ def parse():
     ap.add_argument("--stream-groups", type=int, default=None, help="ResNet inference: image groups on separate "
                     "streams (default: the model's)")
     ap.add_argument("--stream-offset", type=int, default=None, help="ResNet inference: stagger of the stream groups")
-    ap.add_argument("--cpu-iters", type=int, default=3, help="frames timed for the CPU baseline (median; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-launch spans and stage events inside the timed "
+                         "steps, the roofline objects, the H2D-inclusive steps and the CPU baselines.  Off by default: "
+                         "a plain run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (bev, and the encoder's feats) "
+                         "to DIR/<name>.npy as float32 (rank 0 only); an array above DUMP_MAX_ELEMS elements is "
+                         "written as a fixed seeded sample of its flattened elements")
+    ap.add_argument("--cpu-iters", type=int, default=3, help="--full: frames timed for the CPU baseline (median; "
+                                                             "0 = skip)")
     ap.add_argument("--warp-only", action="store_true", help="time only the fused warp (for profiling)")
     ap.add_argument("--warp-nhwc", action="store_true", help="A/B: the fused warp writes its output channels-last "
                     "(bev_ipm_warp_fuse_nhwc_f32) instead of the default NCHW storage")
@@ -350,16 +372,20 @@ def workload(args, world):
 
 def timed_steps(step, steps: int, sync, world: int):
     """The contract's timed region: barrier + sync, exactly `steps` steps, barrier + sync, then the MAX of the
-    elapsed time over the ranks (all_reduce MAX on the default group).  Returns (elapsed_s, own_elapsed_s)."""
+    elapsed time over the ranks (all_reduce MAX on the default group).  Returns (elapsed_s, own_elapsed_s, what the
+    last step returned); every earlier step's result is dropped before the next step starts, as a caller that
+    consumes each result would."""
     def barrier():
         if world > 1:
             torch.distributed.barrier()
         sync()
 
+    last = None
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step(True)
+        last = None
+        last = step(True)
     barrier()
     own = time.perf_counter() - t0
     elapsed = own
@@ -369,7 +395,51 @@ def timed_steps(step, steps: int, sync, world: int):
         t = torch.tensor([own], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
-    return elapsed, own
+    return elapsed, own, last
+
+
+def headline(args, world, value, elapsed, B, V, VL, C, nat) -> dict:
+    """The result line of a plain run: the headline figure, the workload it timed and the library that ran it.
+    --full adds its objects to this same line."""
+    label, wl = workload(args, world)
+    prov = nat.provenance()  # the library this run loaded, and whether it was built from this tree's sources
+    return {
+        "metric": "IPM warp+mean launches/sec (warp-only profiling mode)" if args.warp_only else
+                  "multi-cam frames/sec (7-cam→480×1440 BEV)" if label == "BASELINE configs[1]" else
+                  f"multi-cam frames/sec ({V}-cam→{args.bev[0]}×{args.bev[1]} BEV)",
+        "value": round(value, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "strong" if args.camera_shard else "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"{wl} ({label})", "baseline_config": label,
+                   "frames_per_gpu_per_step": None if args.camera_shard else B,
+                   "batch_source": ("camera-sharded: one frame per step" if args.camera_shard else
+                                    "reference inference batch: inference.py:27, configs/wildtrack.yaml:2"
+                                    if B == 2 else "--batch"),
+                   "frames_per_step": B if args.camera_shard else world * B, "cameras": V,
+                   "cameras_per_gpu": VL, "bev": list(args.bev), "channels": C,
+                   "bev_memory_format": ("n/a" if args.camera_shard else
+                                         "channels_last (--warp-nhwc)" if args.warp_nhwc else "NCHW"),
+                   "parallelism": (f"camera-sharded x{world} (reduce-scatter over BEV rows)" if args.camera_shard
+                                   else f"frame-sharded x{world} (no collective)")},
+        "build": {"lib_source_hash": prov["lib_source_hash"], "tree_source_hash": prov["tree_source_hash"],
+                  "matches_tree": prov["matches_tree"]},
+    }
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array of the last timed step as out_dir/<name>.npy, float32, in its logical (NCHW /
+    B,V,C,H,W) element order whatever its storage.  An array of at most DUMP_MAX_ELEMS elements is written whole, with
+    its shape; a larger one as the 1-D sample of its flattened elements at DUMP_MAX_ELEMS sorted indices drawn by
+    numpy's default_rng(DUMP_SEED) -- a function of the element count alone, so two runs of the same command sample the
+    same elements.  Two arrays: at most 2 x 6 M x 4 B = 48 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def dry_run(args, world: int, rank: int) -> None:
@@ -386,7 +456,7 @@ def dry_run(args, world: int, rank: int) -> None:
 
     for _ in range(args.warmup):
         step(False)
-    elapsed, own = timed_steps(step, args.steps, lambda: None, world)
+    elapsed, own, _ = timed_steps(step, args.steps, lambda: None, world)
     owns = [own]
     if world > 1:
         g = [torch.zeros(1, dtype=torch.float64) for _ in range(world)]
@@ -468,6 +538,7 @@ def main():
     ev = []  # (t0, t1, t2) per timed step: backbone [t0,t1], geometry (+ exchange) [t1,t2]
 
     def step(record):
+        record = record and args.full  # the stage events belong to --full
         with torch.no_grad():
             e0 = e1 = e2 = None
             if record:
@@ -505,9 +576,22 @@ def main():
         torch.cuda.synchronize(dev)
 
     barrier()
-    nat.spans_start()  # HIP events around every conv / warp launch, on the launch stream
-    elapsed, _ = timed_steps(step, args.steps, lambda: torch.cuda.synchronize(dev), world)
-    spans = nat.spans_stop()
+    if args.full:
+        nat.spans_start()  # HIP events around every conv / warp launch, on the launch stream
+    elapsed, _, last = timed_steps(step, args.steps, lambda: torch.cuda.synchronize(dev), world)
+    spans = nat.spans_stop() if args.full else {}
+    frames = (B if args.camera_shard else world * B) * args.steps
+    value = frames / elapsed
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, {"feats": last[0], "bev": last[1]})
+    del last
+
+    if not args.full:  # a plain run ends here
+        if rank == 0:
+            print(json.dumps(headline(args, world, value, elapsed, B, V, VL, C, nat)), flush=True)
+        if dist:
+            torch.distributed.destroy_process_group()
+        return
 
     h2d = None
     if world == 1 and not args.warp_only:
@@ -529,8 +613,6 @@ def main():
     conv_ms = float(np.sum(spans.get("conv", [0.0])) + np.sum(spans.get("dwconv", [0.0]))) / args.steps
     wp_ms = float(np.mean(spans["warp_fuse"]))  # the fused warp kernel only
     box_ms = float(np.mean(spans["warp_boxes"])) if spans.get("warp_boxes") else 0.0  # its footprint-box pre-pass
-    frames = (B if args.camera_shard else world * B) * args.steps
-    value = frames / elapsed
 
     if rank == 0:
         pmc = pmc_traffic(args, world)
@@ -584,7 +666,6 @@ def main():
                    "timing": "HIP events on the launch stream around the fused kernel launch alone (its footprint-box "
                              "pre-pass, k_warp_boxes, and the homographies run before the span, inside the geometry "
                              "stage)"}
-        label, wl = workload(args, world)
         roof_bb_hbm = None
         if not args.warp_only and args.backbone.startswith("efficientnet"):
             # EfficientNet trunk: depthwise / pointwise layers stream their tensors -- HBM-bound, not MFMA-bound
@@ -597,27 +678,10 @@ def main():
                            "timing": "HIP events on the caller stream around the whole encoder stage",
                            "bytes": "each launch reads its input once and writes its output once (+ residual), "
                                     "fp32 NHWC (bench.backbone_bytes)"}
-        line = {
-            "metric": "multi-cam frames/sec (7-cam→480×1440 BEV)" if label == "BASELINE configs[1]" else
-                      f"multi-cam frames/sec ({V}-cam→{args.bev[0]}×{args.bev[1]} BEV)",
-            "value": round(value, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "strong" if args.camera_shard else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"{wl} ({label})", "baseline_config": label,
-                       "frames_per_gpu_per_step": None if args.camera_shard else B,
-                       "batch_source": ("camera-sharded: one frame per step" if args.camera_shard else
-                                        "reference inference batch: inference.py:27, configs/wildtrack.yaml:2"
-                                        if B == 2 else "--batch"),
-                       "frames_per_step": B if args.camera_shard else world * B, "cameras": V,
-                       "cameras_per_gpu": VL, "bev": list(args.bev), "channels": C,
-                       "bev_memory_format": ("n/a" if args.camera_shard else
-                                             "channels_last (--warp-nhwc)" if args.warp_nhwc else "NCHW"),
-                       "parallelism": (f"camera-sharded x{world} (reduce-scatter over BEV rows)" if args.camera_shard
-                                       else f"frame-sharded x{world} (no collective)")},
-            "roofline": roof_bb_hbm or roof_bb or roof_wp,
-            "roofline_warp": roof_wp,
-        }
+        line = headline(args, world, value, elapsed, B, V, VL, C, nat)
+        build = line.pop("build")  # after the roofline objects, as before
+        line["roofline"] = roof_bb_hbm or roof_bb or roof_wp
+        line["roofline_warp"] = roof_wp
         if roof_bb_hbm:
             line["roofline_mfma"] = roof_bb
         if args.camera_shard:
@@ -625,13 +689,9 @@ def main():
                                             "includes the reduce-scatter and the /V"
         if pmc:
             line["traffic_source"] = pmc["source"]
-        prov = nat.provenance()  # the library this run loaded, and whether it was built from this tree's sources
-        line["build"] = {"lib_source_hash": prov["lib_source_hash"], "tree_source_hash": prov["tree_source_hash"],
-                         "matches_tree": prov["matches_tree"]}
+        line["build"] = build
         if h2d:
             line["h2d_inclusive"] = h2d
-        if args.warp_only:
-            line["metric"] = "IPM warp+mean launches/sec (warp-only profiling mode)"
         if world == 1 and args.cpu_iters > 0 and not args.warp_only:
             line["cpu_baseline"] = cpu_baseline(enc, args, K, Rt)
             if not args.camera_shard and args.views == 7 and tuple(args.img) == (1080, 1920):
