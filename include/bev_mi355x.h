@@ -33,7 +33,7 @@ extern "C" {
 #define BEV_FUSE_MEAN 1
 #define BEV_FUSE_MAX 2
 
-/* ABI version (bumped on any signature change). */
+/* ABI version (bumped on any signature change): 13. */
 int bev_abi_version(void);
 
 /* host: provenance -- the first 16 hex digits of sha256 over the library's HIP sources and headers (the
@@ -506,6 +506,19 @@ int bev_conv2d_h16_bnstats_f32(const float *x, int N, int H, int W, int Ci, cons
 int bev_conv2d_h16_ex_f32(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
                           const float *bias, const float *residual, int Co, int KH, int KW, int stride, int pad,
                           int dilation, int act, float *y, int ldy, int Ho, int Wo, float *tile_stats, void *stream);
+
+/* The "f16" inference arithmetic (the reference validates in eval() under autocast(float16), train.py:285-286):
+ * bev_conv2d_h16_ex_f32's convolution with fp16 activations from layer to layer,
+ *     y = f16_rne( act( sum_k f16(x) * packed + bias (+ float(residual)) ) )
+ * x NHWC stored in fp32 (x_half = 0: rounded to fp16 while staging) or fp16 (x_half = 1), packed the
+ * bev_conv_pack_weights_h16 panel, bias fp32 (may be NULL), residual (may be NULL) and y dense NHWC fp16
+ * [N][Ho][Wo][Co] (uint16 storage of _Float16), fp32 accumulation, act 0 / 1 (ReLU) / 2 (SiLU).  Rounding points: the
+ * operands (x once, the weights when packed) and the result, ONCE, after bias, residual and act -- every output is
+ * the value bev_conv2d_h16_ex_f32 computes, rounded to nearest even.  Ci % 64 == 0, Co % 8 == 0, x / packed / y /
+ * residual 16-B aligned, y not overlapping residual; anything else returns BEV_ERR_ARGS.  N == 0 is a no-op. */
+int bev_conv2d_h16_h16(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
+                       const float *bias, const uint16_t *residual, int Co, int KH, int KW, int stride, int pad,
+                       int dilation, int act, uint16_t *y, int Ho, int Wo, void *stream);
 
 /* Weight gradient of a convolution under autocast(float16): dW[co][(ky*KW + kx)*Ci + ci] =
  * sum over output pixels of f16(dz) * f16(x) with fp32 accumulation (the fp16 matrix cores), dW [Co][KH*KW*Ci]

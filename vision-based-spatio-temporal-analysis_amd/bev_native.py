@@ -20,7 +20,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libbev_mi355x.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 BEV_ERR_ARGS = -1  # include/bev_mi355x.h: an argument the kernel cannot take
 
 FUSE_MODES = {"sum": 0, "mean": 1, "max": 2}
@@ -136,6 +136,7 @@ SIGNATURES = {
     "bev_conv2d_h16_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i,
                                    _vp, _vp]),
     "bev_conv_wgrad_h16_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "bev_conv2d_h16_h16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "bev_batchnorm_apply_ex_f32": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "bev_batchnorm_bwd_ex_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp,
                                       _vp, _vp]),
@@ -311,7 +312,12 @@ _AMP_LOCAL = threading.local()
 # the six partial products above 2^-27 relative on the bf16 matrix cores, fp32 accumulation: an fp32 convolution as
 # accurate as the exact-f32 MFMA kernels at 2.67x their matrix-core rate (tests/test_conv_x6_gpu.py measures both
 # against float64); "f32" = bev_conv2d_f32 and the chained bottleneck kernels (exact-f32 MFMA, bitwise an fmaf chain).
-CONV_ARITHS = ("f32", "bf16x6")
+# "f16" (opt-in; ResNet trunks) = bev_conv2d_h16_h16 -- what the reference's validation forward computes in eval()
+# under autocast(float16) (train.py:285-286): fp16 weights and activations on the fp16 matrix cores, fp32
+# accumulation, each conv output (after bias, residual and ReLU) rounded once to fp16 and kept in fp16 from layer to
+# layer; the stem stays in the split arithmetic and writes fp32 (wider than autocast), the encoder's 1x1 proj reads
+# the fp16 trunk output and writes fp32.  The default stays "bf16x6", also under autocast.
+CONV_ARITHS = ("f32", "bf16x6", "f16")
 _ARITH = {"mode": "bf16x6"}
 
 
@@ -917,10 +923,11 @@ def _require_gpu_h(*ts):
 
 def conv2d_h16_any(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: int, KW: int, stride: int, pad: int,
                    stats: bool = False, residual: torch.Tensor = None, bias: torch.Tensor = None, dilation: int = 1,
-                   out: torch.Tensor = None):
+                   out: torch.Tensor = None, act: int = 0):
     """The autocast fp16 conv with x [N,H,W,Ci] stored in fp32 or fp16 (Ci % 64 == 0 for fp16) -> z fp32
     [N,Ho,Wo,Co] (+ residual), and with `stats` the BatchNorm tile partials (conv2d_nhwc_h16_bnstats).  `out`: a
-    wider NHWC fp32 buffer [N,Ho,Wo,>=Co] whose first Co channels receive z (the rest are left as they are)."""
+    wider NHWC fp32 buffer [N,Ho,Wo,>=Co] whose first Co channels receive z (the rest are left as they are); `act`
+    (0 / 1 ReLU / 2 SiLU; not with `stats`) is applied after bias and residual."""
     x = x.contiguous()
     _require_gpu_h(x)
     _require_gpu(residual, bias)
@@ -944,10 +951,55 @@ def conv2d_h16_any(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: int, KW: 
         residual = residual.contiguous()
     with _span("conv", x):
         rc = lib().bev_conv2d_h16_ex_f32(_ptr(x), int(x.dtype == torch.float16), N, H, W, Ci, _ptr(packed),
-                                         _ptr(bias), _ptr(residual), Co, KH, KW, stride, pad, dilation, 0, _ptr(z),
-                                         z.shape[3], Ho, Wo, _ptr(tiles), _stream(x))
+                                         _ptr(bias), _ptr(residual), Co, KH, KW, stride, pad, dilation, int(act),
+                                         _ptr(z), z.shape[3], Ho, Wo, _ptr(tiles), _stream(x))
     _check(rc, "bev_conv2d_h16_ex_f32")
     return (z, tiles) if stats else z
+
+
+def conv2d_h16_half(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, Co: int, KH: int, KW: int, stride: int,
+                    pad: int, dilation: int = 1, act: int = 0, residual: torch.Tensor = None,
+                    out: torch.Tensor = None) -> torch.Tensor:
+    """The "f16" inference conv (bev_conv2d_h16_h16): x [N,H,W,Ci] NHWC stored in fp32 or fp16 (Ci % 64 == 0), the
+    fp16 panel of pack_conv_weight_h16, fp32 bias (or None), fp16 NHWC residual [N,Ho,Wo,Co] (or None) ->
+    y = f16(act(conv + bias + residual)) fp16 NHWC [N,Ho,Wo,Co] (Co % 8 == 0), rounded once.  `out`: a dense fp16
+    [N,Ho,Wo,Co] buffer to write (not the residual)."""
+    x = x.contiguous()
+    _require_gpu_h(x)
+    _require_gpu(bias)
+    if not packed.is_cuda or packed.dtype != torch.float16:
+        raise HipError("conv2d_h16_half needs the fp16 weight panel on the device")
+    N, H, W, Ci = x.shape
+    Ho = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
+    if residual is not None:
+        if not residual.is_cuda or residual.dtype != torch.float16 or tuple(residual.shape) != (N, Ho, Wo, Co):
+            raise HipError("conv2d_h16_half: the residual is an fp16 NHWC device tensor of the output's shape")
+        residual = residual.contiguous()
+    if out is not None:
+        if not (out.is_cuda and out.dtype == torch.float16 and tuple(out.shape) == (N, Ho, Wo, Co)
+                and out.is_contiguous()):
+            raise HipError("conv2d_h16_half: out is a dense fp16 NHWC device tensor of the output's shape")
+        y = out
+    else:
+        y = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float16)
+    with _span("conv", x):
+        rc = lib().bev_conv2d_h16_h16(_ptr(x), int(x.dtype == torch.float16), N, H, W, Ci, _ptr(packed), _ptr(bias),
+                                      _ptr(residual), Co, KH, KW, stride, pad, dilation, int(act), _ptr(y), Ho, Wo,
+                                      _stream(x))
+    _check(rc, "bev_conv2d_h16_h16")
+    return y
+
+
+def pack_conv_weight_h16(w: torch.Tensor) -> torch.Tensor:
+    """OIHW fp32 (device) -> the fp16 panel (RNE) of the fp16 conv kernels, whatever the autocast state."""
+    w = w.detach().contiguous()
+    _require_gpu(w)
+    Co, Ci, KH, KW = w.shape
+    n = lib().bev_conv_packed_size_h16(Co, Ci, KH, KW)
+    out = torch.empty(n, device=w.device, dtype=torch.float16)
+    _check(lib().bev_conv_pack_weights_h16(_ptr(w), Co, Ci, KH, KW, _ptr(out), _stream(w)), "bev_conv_pack_weights_h16")
+    return out
 
 
 def conv_wgrad_h16_any(x: torch.Tensor, dz: torch.Tensor, KH: int, KW: int, stride: int, pad: int,

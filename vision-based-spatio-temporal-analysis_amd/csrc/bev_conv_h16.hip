@@ -303,7 +303,15 @@ __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&ac
 // through an out-of-range offset, which the buffer returns as zeros; the weight panel's K step is the SGPR soffset.
 // Same values in LDS, so results are identical to the pointer form (r05q counters: ~7 VALU per MFMA there, mostly
 // 64-bit address arithmetic).
-template <bool HIN, int BN, bool BUF = false>
+// HOUT (the "f16" inference arithmetic, bev_conv2d_h16_h16): a.y and a.res point to dense fp16 [M][Co] tensors
+// (Co % 8 == 0).  After the last K step the accumulators + bias go to the idle staging LDS as an fp32 [128][BN + 4]
+// tile (rows of BN + 4 words: the 16-lane groups of a ds_read_b128 fall on two rows, 4 mod 8 words apart); each lane
+// reads back 8 consecutive channels of one row, adds the residual (one 16-B load), applies act in fp32, rounds ONCE
+// (RNE) and stores 16 B -- a wave writes four 256-B (BN 64: eight 128-B) row segments per store instruction instead
+// of 2 B per lane at a pixel stride.  Same mainloop, same (acc + bias) + residual order as the fp32 epilogue: every
+// output is the fp32-output kernel's value rounded to fp16.  A template parameter, not a runtime branch: the
+// HOUT = false instances are unchanged.
+template <bool HIN, int BN, bool BUF = false, bool HOUT = false>
 __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
     constexpr int TI = BN == 128 ? 2 : 1, WROWS = BN == 128 ? 64 : 32, NBU = BN == 128 ? 4 : 2;
     __shared__ __attribute__((aligned(16))) _Float16 lds[2][(HBM + BN) * HROW2];
@@ -502,6 +510,48 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
 #undef H16_MFMA
 #undef H16_SWRITE
 #undef H16_GLOAD
+    if constexpr (HOUT) {
+        constexpr int LDW = BN + 4;             // words per row of the fp32 output tile
+        constexpr int LPR = BN / 8, RPP = 256 / LPR;  // lanes per tile row (8 channels each), rows per pass
+        static_assert(HBM * LDW * sizeof(float) <= sizeof(lds), "output tile fits the staging buffers");
+        float *ct = reinterpret_cast<float *>(&lds[0][0]);
+        __syncthreads();  // the last K step's fragment reads are done: both buffers are free
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int c = wn * 64 + j * 32 + r32;
+                const float bv = (a.bias && n0 + c < a.Co) ? a.bias[n0 + c] : 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    ct[(wm * WROWS + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LDW + c] = acc[i][j][r] + bv;
+            }
+        __syncthreads();
+        const int cl = tid % LPR, rr = tid / LPR;
+        const int col = n0 + 8 * cl;
+        const _Float16 *res = reinterpret_cast<const _Float16 *>(a.res);
+        _Float16 *y = reinterpret_cast<_Float16 *>(a.y);
+        if (col < a.Co) {  // Co % 8 == 0: a lane's 8 channels are all inside or all outside
+#pragma unroll
+            for (int p = 0; p < HBM / RPP; ++p) {
+                const int row = rr + RPP * p;
+                const int64_t m = m0 + row;
+                if (m >= a.M) continue;
+                const f32x4 v0 = *(const f32x4 *)(ct + row * LDW + 8 * cl);
+                const f32x4 v1 = *(const f32x4 *)(ct + row * LDW + 8 * cl + 4);
+                float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                if (res) {
+                    const h16x8 rv = *(const h16x8 *)(res + m * a.Co + col);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
+                }
+                h16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = (_Float16)act_h(v[e], a.act);  // the one rounding (RNE)
+                *(h16x8 *)(y + m * a.Co + col) = o;
+            }
+        }
+    } else {
     if (a.stats) h16_tile_stats<BN, TI>(a, acc, lds[0], m0, n0, wm, wn, r32, h);
 #pragma unroll
     for (int i = 0; i < TI; ++i)
@@ -525,6 +575,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
                 a.y[row * a.ldy + col] = act_h(v, a.act);
             }
         }
+    }
 }
 
 // ---- weight gradient under autocast(float16): dW[co][k] = sum_m f16(dz[m][co]) * f16(im2col(x)[m][k]) ----------
@@ -1164,6 +1215,49 @@ static int conv_h16(const void *xv, int x_half, int N, int H, int W, int Ci, con
     }
     else
         hipLaunchKernelGGL(k_conv_h16, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int bev_conv2d_h16_h16(const void *xv, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
+                       const float *bias, const uint16_t *residual, int Co, int KH, int KW, int stride, int pad,
+                       int dilation, int act, uint16_t *y, int Ho, int Wo, void *stream) {
+    if (!xv || !packed || !y || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
+        pad < 0 || dilation <= 0 || act < 0 || act > 2)
+        return BEV_ERR_ARGS;
+    if (Ci % HBK2 != 0 || Co % 8 != 0) return BEV_ERR_ARGS;  // k_conv_h16b's K step; 16-B groups of 8 output channels
+    if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 ||
+        Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1 || Ho <= 0 || Wo <= 0)
+        return BEV_ERR_ARGS;
+    if ((((uintptr_t)xv | (uintptr_t)packed | (uintptr_t)y | (uintptr_t)residual) & 15) != 0) return BEV_ERR_ARGS;
+    ConvH a;
+    a.M = (int64_t)N * Ho * Wo;
+    if (residual) {  // the epilogue reads the residual of a pixel other lanes may already have written: no aliasing
+        const uintptr_t yb = (uintptr_t)y, rb = (uintptr_t)residual, bytes = (uintptr_t)a.M * Co * 2;
+        if (yb == rb || (yb < rb + bytes && rb < yb + bytes)) return BEV_ERR_ARGS;
+    }
+    if (N == 0) return 0;
+    a.x = x_half ? nullptr : (const float *)xv;
+    a.xh = x_half ? (const _Float16 *)xv : nullptr;
+    a.wp = (const _Float16 *)packed;
+    a.bias = bias;
+    a.res = reinterpret_cast<const float *>(residual);  // fp16 [M][Co] in the HOUT instances
+    a.y = reinterpret_cast<float *>(y);                 // ... and fp16 [M][Co]
+    a.stats = nullptr;
+    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
+    a.dil = dilation, a.Ho = Ho, a.Wo = Wo, a.act = act, a.ldy = Co;
+    a.Kp = (int)kpad_h(Ci * KH * KW);
+    // tile widths as in conv_h16 (CONV_H16_KERNEL 2 / 3 force one; 1 has no fp16-output form and runs as 0)
+    const bool n64 = (Co <= 64 && g_h16_kernel != 2) || g_h16_kernel == 3;
+    const int64_t blocks = ((a.M + HBM - 1) / HBM) * (n64 ? (Co + 63) / 64 : (Co + HBN - 1) / HBN);
+    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
+    const bool buf = H16B_BUF && H16B_LINES && x_half && (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
+                     copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
+    void (*kern)(ConvH) =
+        n64 ? (x_half ? (buf ? k_conv_h16b<true, 64, true, true> : k_conv_h16b<true, 64, false, true>)
+                      : k_conv_h16b<false, 64, false, true>)
+            : (x_half ? (buf ? k_conv_h16b<true, 128, true, true> : k_conv_h16b<true, 128, false, true>)
+                      : k_conv_h16b<false, 128, false, true>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

@@ -91,9 +91,13 @@ class CNNEncoder(ViewEncoder):
             if self._feature_channels is None:
                 self._feature_channels = feat.shape[-1]
                 self.proj = nn.Conv2d(self._feature_channels, self.out_channels, kernel_size=1).to(feat.device)
-                self._fproj = FoldedConv(self.proj, split_ok=True)
+                # half_ok (ResNet trunks): in the "f16" arithmetic the proj reads the trunk's fp16 output through
+                # the fp16 matrix-core kernel and writes fp32 -- the warp, fusion and head stay fp32
+                self._fproj = FoldedConv(self.proj, split_ok=True, half_ok=self.backbone_name in _RESNETS)
             if torch.is_grad_enabled() and (self.proj.weight.requires_grad or self.proj.bias.requires_grad):
                 return Proj1x1.apply(feat, self.proj.weight, self.proj.bias)  # trainable proj (BASELINE config 3)
+            if self._fproj.arith() == "f16":
+                return self._fproj(feat, relu=False, f32_out=True)
             if self.proj_stream_nt:
                 # The projection is the last reader of the trunk output (~8x the feature maps' bytes): streamed
                 # with non-temporal loads it no longer evicts the maps it writes from the Infinity Cache, and the

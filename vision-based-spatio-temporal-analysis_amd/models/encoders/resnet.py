@@ -100,13 +100,18 @@ class FoldedConv:
     With `split_ok` (the ResNet trunk and the encoder proj) an NHWC conv with Ci % 16 == 0 runs in the
     arithmetic bev_native.conv_arith() selects: "bf16x6" packs the split-bf16 panel (bev_conv2d_x6_f32), "f32"
     the exact-f32 MFMA panel (bev_conv2d_f32).  The chained bottleneck kernels always take the fp32 panel.
+    With `half_ok` as well (the ResNet trunk and its proj) the "f16" arithmetic applies where Ci % 64 == 0 and
+    Co % 8 == 0: BN is folded in fp32, the folded weights are rounded once into the fp16 panel (its own cache key),
+    and the conv reads fp32 or fp16 NHWC and writes fp16 (bev_conv2d_h16_h16), or fp32 with `f32_out` (the proj).
+    Convs the "f16" arithmetic does not apply to run in that mode as they do in "bf16x6".
     """
 
-    def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d = None, split_ok: bool = False):
+    def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d = None, split_ok: bool = False, half_ok: bool = False):
         self.conv, self.bn = conv, bn
         self.split_ok = split_ok
+        self.half_ok = half_ok
         self._keys = {}
-        self.packed = self.packed6 = self.bias = None
+        self.packed = self.packed6 = self.packed16 = self.bias = None
 
     def _tensors(self):
         ts = [self.conv.weight] + ([self.conv.bias] if self.conv.bias is not None else [])
@@ -116,16 +121,20 @@ class FoldedConv:
 
     def arith(self) -> str:
         c = self.conv
-        if (self.split_ok and _nat.conv_arith() == "bf16x6" and c.in_channels % 16 == 0 and c.groups == 1
-                and c.dilation == (1, 1)):
+        mode = _nat.conv_arith()
+        ok = self.split_ok and c.groups == 1 and c.dilation == (1, 1)
+        if ok and self.half_ok and mode == "f16" and c.in_channels % 64 == 0 and c.out_channels % 8 == 0:
+            return "f16"
+        if ok and mode in ("bf16x6", "f16") and c.in_channels % 16 == 0:
             return "bf16x6"
         return "f32"
 
     def stem_x6(self) -> bool:
         """The ResNet stem (7x7 / s2 / p3, Ci 3, Co <= 64) under the bf16x6 arithmetic takes the split-arithmetic
-        stem kernel (STEM_X6, default on; off: the exact-f32 stem, fp32-tolerance equal)."""
+        stem kernel (STEM_X6, default on; off: the exact-f32 stem, fp32-tolerance equal).  So it does under "f16":
+        Ci = 3 cannot take the fp16 kernel, the stem stays fp32-class and writes fp32 (wider than autocast's)."""
         c = self.conv
-        return (STEM_X6 and self.split_ok and _nat.conv_arith() == "bf16x6" and c.in_channels == 3
+        return (STEM_X6 and self.split_ok and _nat.conv_arith() in ("bf16x6", "f16") and c.in_channels == 3
                 and c.out_channels <= 64 and c.kernel_size == (7, 7) and c.stride == (2, 2) and c.padding == (3, 3)
                 and c.groups == 1 and c.dilation == (1, 1))
 
@@ -138,6 +147,8 @@ class FoldedConv:
         with torch.no_grad():
             if arith == "bf16x6":
                 self.packed6 = _nat.pack_conv_weight_x6(w.contiguous())
+            elif arith == "f16":
+                self.packed16 = _nat.pack_conv_weight_h16(w.contiguous())  # folded in fp32 above; the pack rounds
             else:
                 self.packed = _nat.pack_conv_weight(w.contiguous())
             self.bias = b.contiguous().float()
@@ -157,10 +168,25 @@ class FoldedConv:
         return w, b
 
     def __call__(self, x, relu: bool, residual=None, in_nchw: bool = False, ascale=None, out=None,
-                 split_out: bool = False):
+                 split_out: bool = False, f32_out: bool = False):
         """x: NHWC fp32 (NCHW with in_nchw) or, in the bf16x6 arithmetic, a bev_native.Split3; split_out (bf16x6
-        only) returns the result as a Split3 -- the pre-split operand of the next conv."""
+        only) returns the result as a Split3 -- the pre-split operand of the next conv.  In the f16 arithmetic x is
+        NHWC fp32 or fp16, the residual fp16, and the result fp16 -- or, with f32_out (no residual), fp32."""
         c = self.conv
+        if not in_nchw and ascale is None and self.arith() == "f16":
+            self.prepare(x.device, "f16")
+            k, s, p = c.kernel_size, c.stride[0], c.padding[0]
+            if f32_out:
+                assert residual is None and not split_out
+                return _nat.conv2d_h16_any(x, self.packed16, c.out_channels, k[0], k[1], s, p, bias=self.bias,
+                                           act=int(relu), out=out)
+            assert not split_out
+            return _nat.conv2d_h16_half(x, self.packed16, self.bias, c.out_channels, k[0], k[1], s, p, 1, int(relu),
+                                        residual=residual, out=out)
+        if isinstance(x, torch.Tensor) and x.dtype == torch.float16:  # an fp16 edge into a conv outside the f16 rules
+            x = x.float()
+        if residual is not None and residual.dtype == torch.float16:
+            residual = residual.float()
         if in_nchw and self.stem_x6():  # the stem on the split arithmetic (bev_conv2d_stem_x6_f32)
             self.prepare(x.device, "bf16x6")
             return _nat.conv2d_stem_x6(x, self.packed6, self.bias, c.out_channels, relu, out=out)
@@ -371,7 +397,7 @@ class ResNet(nn.Module):
     def _fc(self, conv, bn):
         k = id(conv)
         if k not in self._folded:
-            self._folded[k] = FoldedConv(conv, bn, split_ok=True)
+            self._folded[k] = FoldedConv(conv, bn, split_ok=True, half_ok=True)
         return self._folded[k]
 
     def unexecuted_parameter_names(self, out_index: int):
@@ -431,6 +457,13 @@ class ResNet(nn.Module):
             H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         return x.shape[0], H, W, self.feature_info[oi]
 
+    def _out_dtype(self, out_index: int):
+        """fp16 where the eval chain's last conv runs in the "f16" arithmetic (it writes fp16), else fp32."""
+        if out_index < 1:
+            return torch.float32
+        conv, bn, _ = (self.layer1, self.layer2, self.layer3, self.layer4)[min(out_index, 4) - 1][-1].convs()[-1]
+        return torch.float16 if self._fc(conv, bn).arith() == "f16" else torch.float32
+
     def _prepare_eval(self, device, out_index: int):
         """Fold + pack every conv the eval chain up to `out_index` runs, on the caller's stream.  Called
         before the image groups fork onto their side streams, so no group can read a panel (or a freed old
@@ -458,7 +491,7 @@ class ResNet(nn.Module):
         side = self._streams.setdefault(dev, [])
         while len(side) < G:
             side.append(torch.cuda.Stream(device=dev))
-        out = torch.empty(self._out_shape(x, out_index), device=dev, dtype=torch.float32)
+        out = torch.empty(self._out_shape(x, out_index), device=dev, dtype=self._out_dtype(out_index))
         bounds = [x.shape[0] * g // G for g in range(G + 1)]
         prev = None  # group g starts once group g - 1 has passed launch stage `stream_offset`
         for g in range(G):
@@ -538,6 +571,11 @@ class ResNet(nn.Module):
         """(kind, folded executors) of one residual block on the eval path.  The chained kernels are exact-f32
         MFMA kernels: with the split-bf16 arithmetic (bev_native.conv_arith() == "bf16x6") the block runs as
         separate split-bf16 launches (conv1, conv2, conv3 + shortcut as one dual GEMM) instead."""
+        if _nat.conv_arith() == "f16":
+            # fp16 activations from layer to layer: downsample -> fp16 shortcut, conv1, conv2 -> fp16, the last conv
+            # adds the fp16 residual and applies ReLU in its epilogue.  No chained / dual kernels (fp32-class only).
+            ds = self._fc(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None
+            return "plain", [ds] + [self._fc(conv, bn) for conv, bn, _ in blk.convs()]
         stage = self._stage_of_block(blk)
         chains = self.fuse_chain and (_nat.conv_arith() == "f32" or stage in self.f32_chain_stages)
         if (isinstance(blk, Bottleneck) and self.fuse_chain and not chains and stage in self.x6_chain_stages
@@ -613,6 +651,10 @@ class ResNet(nn.Module):
         sc = fs[0](x, relu=False) if fs[0] is not None else x
         chain = blk.convs()
         fl = fs[1:]
+        if fs[0] is None and fl[-1].arith() == "f16" and x.dtype != torch.float16:
+            # an identity shortcut from the fp32 stem (BasicBlock layer1.0): the fp16 residual is the block input
+            # rounded once -- the value conv1 rounds it to while staging, so conv1 reads the rounded copy too
+            x = sc = x.half()
         y = x
         for idx, ((conv, bn, relu), f) in enumerate(zip(chain, fl)):
             last = idx == len(chain) - 1
