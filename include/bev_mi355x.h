@@ -33,7 +33,7 @@ extern "C" {
 #define BEV_FUSE_MEAN 1
 #define BEV_FUSE_MAX 2
 
-/* ABI version (bumped on any signature change): 13. */
+/* ABI version (bumped on any signature change): 14. */
 int bev_abi_version(void);
 
 /* host: provenance -- the first 16 hex digits of sha256 over the library's HIP sources and headers (the
@@ -45,11 +45,11 @@ const char *bev_build_source_hash(void);
  * BEV_TUNE_CONV_TILE: 0 = automatic, 1 = 128x128, 2 = 128x64, 3 = 64x128, 4 = 64x64
  *   output tiles for bev_conv2d_f32.
  * BEV_TUNE_WARP_POOL_KB: LDS footprint-image pool per workgroup of the fused warp in KiB, 0 = automatic,
- *   else 1..150 (small pools force one-view batches / direct views in the default kernel and block
+ *   else 1..150 (small pools force one-view batches / direct views in the DPP-row kernel and block
  *   decomposition in the per-view LDS-DMA kernel, which uses at least 8).
  * BEV_TUNE_WARP_KERNEL: fused warp kernel for NHWC C % 64 == 0 features:
  *   0 = default (= 2), 1 = register-staged, 2 = per-view LDS-DMA kernel, 3 = DPP-row kernel with batched
- *   footprint staging (SUM / MEAN with a workspace; else 2).
+ *   footprint staging (SUM / MEAN with a workspace; else 2; measured slower).
  * BEV_TUNE_WARP_BWD_POOL: LDS image of the warp backward in floats (<= 19968), 0 = 19968.
  * BEV_TUNE_CONV_XCD: 1 (default) = XCD-aware conv block order, 0 = plain.
  * BEV_TUNE_CONV_NBUF: 0 = automatic, 1 / 2 = LDS staging depth of the 128x64 / 64x128 conv tiles.
@@ -82,9 +82,6 @@ const char *bev_build_source_hash(void);
  * BEV_TUNE_STEM3_STAGE: bev_conv2d_stem3_f32 output stores: staged in LDS and written as whole NHWC row runs (1 KiB
  *   per instruction), 64 pixels per wave and pass (1) or 32 (2, default: half the LDS, more resident workgroups);
  *   0 = straight from registers (16 B per lane at a pixel stride).  Same results.
- * BEV_TUNE_WARP_PERSIST: fused warp sum / mean with C == 64, NCHW or rank-chunk-major output and a footprint-box
- *   workspace: 0 (default) = one workgroup per (tile, frame); 1 / 2 = the persistent work-queue kernel with 8 queues
- *   (one per XCD) / one queue (A/B options, measured slower).  Same results.
  * BEV_TUNE_WARP_SPAN: fused warp with a footprint-box workspace: span staging (each box row's tap span only) for
  *   footprints of <= 32 rows -- always where the box does not fit the LDS pool but the spans do, and where it fits
  *   when the spans need at most `value` percent of its pixels (1..100, e.g. 50); 0 (default) = box staging only.
@@ -109,7 +106,7 @@ const char *bev_build_source_hash(void);
 #define BEV_TUNE_DW_RUN 14
 #define BEV_TUNE_CONV_X6_NT 16
 #define BEV_TUNE_STEM3_STAGE 17
-#define BEV_TUNE_WARP_PERSIST 18
+/* 18 (a persistent work-queue fused warp, removed with ABI 14) is not reused */
 #define BEV_TUNE_WARP_SPAN 19
 #define BEV_TUNE_WARP_TILE_BAND 20
 int bev_tune(int knob, int value);
@@ -169,7 +166,8 @@ int bev_ipm_warp_fuse_ws_f32(const float *feats, int64_t sN, int64_t sC, int64_t
  * the same Hmat / xs / ys / B / V / Hf / Wf / sx / sy / Hb / Wb / mode and tuning knobs, ordered before it (same stream
  * or an event); otherwise it is bev_ipm_warp_fuse_ws_f32.  Same results.  The workspace starts with a 16-B header
  * recording the fit test (LDS pool), V and tile shape the boxes were made for; a fused launch whose own differ (another
- * mode's pool, a changed pool knob) ignores the boxes and derives its footprints itself -- still the same results.
+ * mode's pool, a changed pool knob, boxes made with BEV_TUNE_WARP_SPAN on meeting a launch with it off) ignores the
+ * boxes and derives its footprints itself -- still the same results.
  * Replaces the same reference ops (geometry.py:120-162 + fusion.py:17-22). */
 int bev_ipm_warp_fuse_boxes_f32(const float *Hmat, const float *xs, const float *ys, int B, int V, int Hf, int Wf,
                                 float sx, float sy, int Hb, int Wb, int mode, void *workspace, int64_t workspace_bytes,

@@ -48,7 +48,7 @@ def main():
     # a leading "w" times the wave-independent kernel (bev_tune(BEV_TUNE_WARP_KERNEL, 2)); libwarp_ablate_w<b>.so
     # must be a separate copy of the library (its own knob state)
     for b, L in libs.items():
-        if b.startswith("w") or b.startswith("p"):  # "p": the persistent kernel (BEV_TUNE_WARP_KERNEL 3)
+        if b.startswith("w") or b.startswith("p"):  # "p": the DPP-row kernel (BEV_TUNE_WARP_KERNEL 3)
             tune = getattr(L, "_ZN3bev9warp_tuneEii")  # bev::warp_tune (bev_warp.hip alone has no bev_tune)
             tune.restype = ctypes.c_int
             tune.argtypes = [ctypes.c_int, ctypes.c_int]

@@ -1,9 +1,9 @@
-"""Interleaved A/B of the fused warp's persistent kernel (BEV_TUNE_WARP_PERSIST 1, k_warp_fuse_p) against the
-one-workgroup-per-tile kernel (0, k_warp_fuse_v2): bench geometry (7 cams, C = 64 NHWC features 135 x 240 ->
-480 x 1440, B = 2, mean) or the K5 rig (--k5: 16 cams 4K, 270 x 480 maps, sum); footprint boxes computed once,
-HIP events around the fused launches alone; us per launch, HBM fraction of the algorithmic bytes, and a bit check.
+"""Interleaved A/B of one fused-warp knob (k_warp_fuse_v2: the LDS pool, the span-staging threshold or the tile
+order): bench geometry (7 cams, C = 64 NHWC features 135 x 240 -> 480 x 1440, B = 2, mean) or the K5 rig (--k5:
+16 cams 4K, 270 x 480 maps, sum); footprint boxes made per variant outside the timed span, HIP events around the
+fused launches alone; us per launch, HBM fraction of the algorithmic bytes, and a bit check.
 
-    python tools/warp_persist_ab.py [--k5] [--iters 20] [--rounds 4] [--pools 0:40] [--spans 0:80:100] [--bands 1:2:4]
+    python tools/warp_knob_ab.py [--k5] [--iters 20] [--rounds 4] (--pools 0:40 | --spans 0:80:100 | --bands 1:2:4)
 """
 import argparse
 import os
@@ -41,10 +41,9 @@ def main():
     f = torch.randn(B, V, Hf, Wf, 64, device=dev).permute(0, 1, 4, 2, 3)  # NHWC storage
     Kt, Rtt = torch.from_numpy(K).to(dev), torch.from_numpy(Rt).to(dev)
     Hm, xs, ys, hw = g._sampling(f, Kt, Rtt, (H, W))
-    boxes = nat.warp_fuse_boxes(Hm, xs, ys, B, V, Hf, Wf, hw, mode)
     import bench
     alg, _, _ = bench.warp_alg_bytes(g, Hm, tuple(f.shape), (H, W), B)
-    variants = [("persist", 1), ("persist", 2), ("persist", 0)]
+    variants = [("pool", 0)]
     if a.pools:
         variants = [("pool", int(x)) for x in a.pools.replace(":", ",").split(",")]
     if a.spans:
@@ -55,9 +54,9 @@ def main():
     ref = None
     for _ in range(a.rounds):
         for var in variants:
-            knobs = {{"persist": "WARP_PERSIST", "pool": "WARP_POOL_KB", "span": "WARP_SPAN", "band": "WARP_TILE_BAND"}[var[0]]: var[1]}
+            knobs = {{"pool": "WARP_POOL_KB", "span": "WARP_SPAN", "band": "WARP_TILE_BAND"}[var[0]]: var[1]}
             with nat.tuned(**knobs):
-                bx = boxes if var[0] == "persist" else nat.warp_fuse_boxes(Hm, xs, ys, B, V, Hf, Wf, hw, mode)
+                bx = nat.warp_fuse_boxes(Hm, xs, ys, B, V, Hf, Wf, hw, mode)
                 out = nat.warp_fuse(f, Hm, xs, ys, hw, mode, boxes=bx)
                 torch.cuda.synchronize()
                 if ref is None:
@@ -73,8 +72,7 @@ def main():
                 res[var].append(e0.elapsed_time(e1) / a.iters * 1e3)
     for var, v in res.items():
         us = statistics.median(v)
-        name = (["per-tile", "persistent 8 queues", "persistent 1 queue"][var[1]] if var[0] == "persist"
-                else f"pool {var[1]} KiB" if var[0] == "pool" else f"span {var[1]} %" if var[0] == "span"
+        name = (f"pool {var[1]} KiB" if var[0] == "pool" else f"span {var[1]} %" if var[0] == "span"
                 else f"tile band {var[1]}")
         print(f"{name:20s} {us:8.2f} us  frac {alg / (us * 1e-6) / 8e12:.4f}  "
               f"(all: {', '.join(f'{x:.1f}' for x in v)})", flush=True)

@@ -28,6 +28,7 @@
 
 #include "bev_geometry.h"
 #include <algorithm>
+#include <type_traits>
 
 #include "bev_tune.h"
 #include "../../include/bev_mi355x.h"
@@ -419,58 +420,14 @@ __device__ __forceinline__ void dma_block(const float *__restrict__ f, int sH, i
     }
 }
 
-#ifndef WARP_DMA_ROWS
-#define WARP_DMA_ROWS 0  // fused warp v2 staging: 3 pixels of one box row per LDS-DMA instruction (1, A/B: neutral on K2, +4 % on K5) or dma_block (0)
-#endif
-
-// The same image as dma_block (pixel p = py * sbw + px at `off` + 272 p, 17 slots of 16 B: 64 channels + pad) from
-// one LDS-DMA instruction per 3 pixels of a box row.  Lane l moves chunk l % 17 of pixel l / 17 of the instruction
-// (the pad slot and lanes 51-63 stay idle), so its global byte offset from the instruction's first pixel is a
-// per-lane constant; the pixel address itself is an SGPR base (global_load_lds_dwordx4 with saddr) and M0 the
-// instruction's first slot -- the per-instruction work is scalar.  Instructions are dealt round-robin over the
-// waves (row-major), so every wave issues about sbh * ceil(sbw / 3) / nwaves of them.  Element offsets are 32-bit
-// (the launcher checks that a feature map fits).
-__device__ __forceinline__ void dma_rows(const float *__restrict__ f, int sH, int sW, int sx0, int sy0, int sbw,
-                                         int sbh, unsigned char *smem, int off, int wave, int lane,
-                                         int nwaves = FT_NT / 64) {
-    if (WARP_ABLATE & 2) return;
-    const int lp = (lane * 241) >> 12;  // lane / 17 for lane < 64
-    const int ls = lane - 17 * lp;
-    const bool slot_ok = lp < 3 && ls < 16;
-    const unsigned voff = (unsigned)((lp * sW + ls * 4) * (int)sizeof(float));
-    const int per_row = (sbw + 2) / 3;
-    const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base(smem) + (unsigned)off));
-    int py = 0, i = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform: the loop runs on the scalar unit
-    while (i >= per_row && py < sbh) {  // instruction `wave` of the row-major order
-        i -= per_row;
-        ++py;
-    }
-    for (; py < sbh;) {
-        const int rem = sbw - 3 * i;  // pixels left in the row from this instruction's first (>= 1)
-        const float *src = f + (sy0 + py) * sH + (sx0 + 3 * i) * sW;
-        const unsigned dst = lds0 + (unsigned)((py * sbw + 3 * i) * 272);
-        if (slot_ok && lp < rem) {
-            unsigned keep;
-            asm volatile(
-                "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                "global_load_lds_dwordx4 %1, %3" WARP_DMA_POLICY "\n\ts_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "v"(voff), "s"(dst), "s"(src)
-                : "memory");
-        }
-        i += nwaves;
-        while (i >= per_row && py < sbh) {
-            i -= per_row;
-            ++py;
-        }
-    }
-}
-
 // Span staging (see row_span): a footprint staged row by row, row r = the `len` pixels from column `sx` of box row r,
 // rows back to back from LDS byte offset `off` (pixel exc_r + k of the image = column sx_r + k of row r; exc = the
-// exclusive prefix sum of len over the rows).  Lane r of len / sx / exc holds row r's values (r < nrows <= 32).  The
-// same instruction form as dma_rows (3 pixels of one row per LDS-DMA instruction, scalar source base and M0); the
-// instructions of all rows are dealt round-robin over the waves.
+// exclusive prefix sum of len over the rows).  Lane r of len / sx / exc holds row r's values (r < nrows <= 32).
+// One LDS-DMA instruction moves 3 pixels of one row: lane l moves chunk l % 17 of pixel l / 17 of the instruction
+// (the pad slot and lanes 51-63 stay idle), so its global byte offset from the instruction's first pixel is a
+// per-lane constant; the pixel address itself is an SGPR base (global_load_lds_dwordx4 with saddr) and M0 the
+// instruction's first slot.  The instructions of all rows are dealt round-robin over the waves.  Element offsets
+// are 32-bit (the launcher checks that a feature map fits).
 __device__ __forceinline__ void dma_spans(const float *__restrict__ f, int sH, int sW, int sy0, int nrows, int len,
                                           int sxr, int exc, unsigned char *smem, int off, int wave, int lane,
                                           int nwaves = FT_NT / 64) {
@@ -514,27 +471,7 @@ __device__ __forceinline__ uint32_t out_range(size_t total_bytes, size_t base) {
     return r > 0xffffffffull ? 0xffffffffu : (uint32_t)r;
 }
 
-#ifndef WARP_TAPS_AHEAD
-#define WARP_TAPS_AHEAD 0  // fused warp v2: the next live view's taps computed before the end-of-view wait (1), inside
-                           // this view's LDS sampling after group WARP_TAPS_AHEAD - 2 (>= 2), or at its start (0)
-#endif
-#ifndef WARP_STAGE_ALL
-#define WARP_STAGE_ALL 0  // fused warp v2: all live views staged at once when they fit the pool (1, A/B: neutral) or per view (0)
-#endif
-// LDS bytes of an np-pixel footprint image (17-slot pixels); dma_block rounds to its 1-KiB instructions
-#ifndef WARP_CK
-#define WARP_CK 64  // fused warp v2 channels per workgroup: 64 (one workgroup per tile and frame) or 32 (A/B: two
-                    // workgroups per tile, each staging and sampling every other 32-channel group -- half the LDS image
-                    // and accumulator per workgroup, the taps computed twice)
-#endif
-static_assert(WARP_CK == 64 || WARP_CK == 32, "WARP_CK: 64 or 32");
-static_assert(WARP_CK == 64 || WARP_DMA_ROWS == 0, "the row DMA stages 64-channel pixels");
-constexpr int V2_SL = WARP_CK / 4 + 1;  // DMA slots of 16 B per staged pixel (WARP_CK channels + pad)
-constexpr int V2_SPLIT = 64 / WARP_CK;  // workgroups per (tile, frame)
-
-__device__ __forceinline__ int stage_bytes(int np) {
-    return WARP_DMA_ROWS ? np * 272 : ((np * V2_SL + 63) >> 6) * 1024;
-}
+constexpr int V2_SL = 17;  // fused warp v2: DMA slots of 16 B per staged pixel (64 channels + pad)
 
 #ifndef WARP_STORE_AUX
 #define WARP_STORE_AUX 2  // fused warp output stores: buffer cache policy (2 = nt, streaming; 0 = default)
@@ -574,39 +511,17 @@ __device__ unsigned long long g_warp_stamp[16384 * STAMP_N];
 #ifndef WARP_LANESKIP
 #define WARP_LANESKIP 1  // fused warp v2: lanes with no valid tap skip the view's LDS sampling (1, r03 A/B: 1-8 % faster) or read the zero pixel (0)
 #endif
+// acc / V for the mean: div_rcp through double (exact)
+struct MeanDiv {
+    double rV;
+};
+__device__ __forceinline__ MeanDiv mean_div_of(int V) { return MeanDiv{recip_uniform(V)}; }
+__device__ __forceinline__ float mean_div(float a, const MeanDiv &m) { return div_rcp(a, m.rV); }
+
 // Output stores of a 64-channel chunk through a buffer descriptor: SGPR base of
 // the chunk, per-lane byte offset of the cell, SGPR byte offset of the channel
 // plane -> no per-store address arithmetic.  The dispatcher guarantees the
 // chunk (64 planes) spans < 4 GiB.  aux 2 = nt (streaming, written once).
-#ifndef WARP_MEAN_FP32
-#define WARP_MEAN_FP32 0  // fused warp v2 mean: Markstein fp32 division for the exhaustively verified V (1, A/B: slower), or div_rcp (0)
-#endif
-// acc / V for the mean: for V with bit V - 1 of MARKSTEIN_EXACT_V, q0 = a * RN(1/V) and one correction step
-// q0 + RN(a - q0 V) * RN(1/V) (two FMAs) is the correctly rounded quotient for every float but -0 (the view sum is
-// never -0) -- tools/verify_div_markstein_fix.c, exhaustive over all 2^32 inputs; infinities give NaN in the
-// correction, which the fix-up maps back to q0 (= +-inf, the IEEE quotient).  Other V: div_rcp through double.
-struct MeanDiv {
-    float vf, rf;
-    double rV;
-    bool fast;
-};
-__device__ __forceinline__ MeanDiv mean_div_of(int V) {
-    MeanDiv m;
-    m.vf = (float)V;
-    m.rV = recip_uniform(V);
-    m.rf = (float)m.rV;
-    m.fast = WARP_MEAN_FP32 && V >= 1 && V <= 64 && ((MARKSTEIN_EXACT_V >> (V - 1)) & 1ull);
-    return m;
-}
-__device__ __forceinline__ float mean_div(float a, const MeanDiv &m) {
-    if (m.fast) {
-        const float q0 = a * m.rf;
-        const float q = __builtin_fmaf(__builtin_fmaf(-q0, m.vf, a), m.rf, q0);
-        return q != q ? q0 : q;
-    }
-    return div_rcp(a, m.rV);
-}
-
 template <int N>
 __device__ __forceinline__ void store_chunk(float *chunk, size_t plane, int voff, const float (&acc)[N], int mode,
                                             const MeanDiv &md, uint32_t range) {
@@ -773,9 +688,9 @@ constexpr double EPS32 = 5.9604644775390625e-08;  // 2^-24
 constexpr unsigned BOX_MAGIC = 0x42455642u;  // "BVEB"
 constexpr int BOX_HDR = 16;                   // header bytes before the boxes
 constexpr int V2_MAXV = 64;                         // one view per lane
-constexpr int WQ_WORDS = 16;  // queue words after the boxes: [0..7] tickets per queue, [8] finished workgroups
-// Span tables after the queue words ([frame][tile][view][SPAN_ROWS] words, written for the views flagged span-staged:
-// box word a, bit 30).  Header word w = TH | SPAN_FLAG when k_warp_boxes made them.
+// Span tables after the boxes ([frame][tile][view][SPAN_ROWS] words, written for the views flagged span-staged:
+// box word a, bit 30).  Header word w = TH | SPAN_FLAG when k_warp_boxes made them; a view flagged span-staged may
+// be too large for the pool as a box, so only the SPAN instantiation of the fused kernel accepts such a header.
 constexpr int SPAN_ROWS = 32;          // span staging applies to boxes of at most this many rows
 constexpr int SPAN_HDR = 144;          // LDS bytes before a span-staged image: the row bases of rows -1 .. 32 (34 ints)
 constexpr unsigned SPAN_FLAG = 0x100u;
@@ -959,16 +874,11 @@ __device__ __forceinline__ void bilerp4(float (&acc)[N], int q0, const f32x4 &nw
 
 // LDS sampling of one view, software-pipelined by one 4-channel group (PIPE; else
 // each group's reads are issued right before its use -- fewer live registers, the
-// max reduction's choice).  Invalid taps read the zero pixel `zp` (the nw tap: `zp0`,
-// see k_warp_fuse_pc's blocked views).
-struct NoMid {
-    __device__ __forceinline__ void operator()() const {}
-};
-// `mid` runs between LDS groups MID_G and MID_G + 1 (the next view's taps while this view's reads are in flight)
+// max reduction's choice).  Invalid taps read the zero pixel `zp` (the nw tap: `zp0`).
 // (the taps' LDS pixels: (x0, y0) at byte pb, (x0, y0 + 1) at byte pbs, each row's x0 + 1 one pixel further)
-template <int MODE, int N, bool PIPE = true, int MID_G = -1, class Mid = NoMid>
+template <int MODE, int N, bool PIPE = true>
 __device__ __forceinline__ void sample_pipe_at(float (&acc)[N], const Taps &t, const unsigned char *smem, int pb,
-                                               int pbs, int zp, int zp0, Mid mid = Mid()) {
+                                               int pbs, int zp, int zp0) {
     constexpr int PS = (N / 4 + 1) * 16, NG = N / 4;
     const unsigned char *a0 = smem + ((t.valid & 1) ? pb : zp0);
     const unsigned char *a1 = smem + ((t.valid & 2) ? pb + PS : zp);
@@ -980,7 +890,6 @@ __device__ __forceinline__ void sample_pipe_at(float (&acc)[N], const Taps &t, c
             const f32x4 c0 = *(const f32x4 *)(a0 + g * 16), c1 = *(const f32x4 *)(a1 + g * 16);
             const f32x4 c2 = *(const f32x4 *)(a2 + g * 16), c3 = *(const f32x4 *)(a3 + g * 16);
             bilerp4<MODE>(acc, 4 * g, c0, c1, c2, c3, t.w);
-            if (g == MID_G) mid();
             __builtin_amdgcn_sched_barrier(0);
         }
         return;
@@ -1004,7 +913,6 @@ __device__ __forceinline__ void sample_pipe_at(float (&acc)[N], const Taps &t, c
             acc[4 * g] += c0.x + c1.y + c2.z + c3.w;
         } else
         bilerp4<MODE>(acc, 4 * g, c0, c1, c2, c3, t.w);
-        if (g == MID_G) mid();
         __builtin_amdgcn_sched_barrier(0);  // at most two groups of reads in flight
         if (g < NG - 1) {
             c0 = n0;
@@ -1013,15 +921,6 @@ __device__ __forceinline__ void sample_pipe_at(float (&acc)[N], const Taps &t, c
             c3 = n3;
         }
     }
-}
-
-// ... from a box image at LDS byte `ib` (origin sx0, sy0, width sbw)
-template <int MODE, int N, bool PIPE = true, int MID_G = -1, class Mid = NoMid>
-__device__ __forceinline__ void sample_view_pipe(float (&acc)[N], const Taps &t, const unsigned char *smem, int ib,
-                                                 int sx0, int sy0, int sbw, int zp, int zp0, Mid mid = Mid()) {
-    constexpr int PS = (N / 4 + 1) * 16;
-    const int pb = ib + ((t.y0 - sy0) * sbw + (t.x0 - sx0)) * PS;
-    sample_pipe_at<MODE, N, PIPE, MID_G, Mid>(acc, t, smem, pb, pb + sbw * PS, zp, zp0, mid);
 }
 
 // Tile shapes of k_warp_fuse_v2 (TH rows x TW cells, 256 lanes, one cell per lane):
@@ -1044,16 +943,22 @@ __device__ __forceinline__ void tile_cell(int lane, int wave, int &r, int &c) {
     }
 }
 
-template <int MODE, int OCC, int TH = 8, bool CHUNK = false, bool NHWC = false>
-__global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__restrict__ feats, int64_t sN, int64_t sH,
-                                                          int64_t sW, const float *__restrict__ Hmat,
-                                                          const float *__restrict__ xs, const float *__restrict__ ys,
-                                                          int B, int V, int C, int Hf, int Wf, float sx, float sy,
-                                                          int Hb, int Wb, float *__restrict__ out, int pool,
-                                                          const uint2 *__restrict__ boxes_in, int rpr, int tband) {
+#ifndef WARP_OCC
+#define WARP_OCC 3   // workgroups per CU the default (mean / sum) kernel is compiled and sized for
+#endif
+// workgroups per CU by mode: MAX's extra live state spills at 3, so it is compiled and sized for 2
+constexpr int v2_occ(int mode) { return mode == BEV_FUSE_MAX ? 2 : WARP_OCC; }
+
+// SPAN: span staging (BEV_TUNE_WARP_SPAN) -- the instantiation launched with span tables; the span-free one holds
+// none of its code or state.
+template <int MODE, int TH, bool CHUNK, bool NHWC, bool SPAN>
+__global__ __launch_bounds__(FT_NT, v2_occ(MODE)) void k_warp_fuse_v2(
+    const float *__restrict__ feats, int64_t sN, int64_t sH, int64_t sW, const float *__restrict__ Hmat,
+    const float *__restrict__ xs, const float *__restrict__ ys, int B, int V, int C, int Hf, int Wf, float sx, float sy,
+    int Hb, int Wb, float *__restrict__ out, int pool, const uint2 *__restrict__ boxes_in, int rpr, int tband) {
     constexpr int NW = FT_NT / 64;  // 4 waves
     constexpr int TW = FT_NT / TH;  // tile width in cells
-    constexpr int CK = WARP_CK, SL = V2_SL, PS = SL * 16;  // channels / DMA slots / bytes per staged pixel (+ pad)
+    constexpr int CK = 64, SL = V2_SL, PS = SL * 16;  // channels / DMA slots / bytes per staged pixel (+ pad)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int zp = pool;                                    // zero pixel (256 B)
     int *red = reinterpret_cast<int *>(smem + pool + 256);  // [4 * NW] exact-bbox exchange
@@ -1077,13 +982,11 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
     int tr, tc;
     tile_cell<TH>(lane, wave, tr, tc);
     auto dma = [&](const float *fp, int x0, int y0, int w, int h, int o) {
-        if (WARP_DMA_ROWS) dma_rows(fp, (int)sH, (int)sW, x0, y0, w, h, smem, o, wave, lane, NW);
-        else dma_block<SL>(fp, (int)sH, (int)sW, x0, y0, w, w * h, smem, o, wave, lane, NW);
+        dma_block<SL>(fp, (int)sH, (int)sW, x0, y0, w, w * h, smem, o, wave, lane, NW);
     };
     const int i = tyb * TH + tr;
     const int j = txb * TW + tc;
-    const int b = V2_SPLIT == 1 ? (int)blockIdx.y : (int)blockIdx.y / V2_SPLIT;
-    const int cfirst = V2_SPLIT == 1 ? 0 : ((int)blockIdx.y % V2_SPLIT) * CK;  // this workgroup's first channel
+    const int b = blockIdx.y;
     const bool inside = (i < Hb) && (j < Wb);
     const float cx = xs[inside ? j : 0], cy = ys[inside ? i : 0];
     const size_t plane = (size_t)Hb * Wb;
@@ -1155,15 +1058,18 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
     if (tid < 16) *(float4 *)(smem + zp + tid * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
     unsigned *btab = reinterpret_cast<unsigned *>(htab + V2_MAXV * 9);  // [V][2] corner boxes
     bool box_hdr_ok = false;  // boxes made for this kernel's fit test and tiling? (else: computed here)
-    bool span_ok = false;     // ... and span tables for the views flagged span-staged
+    [[maybe_unused]] const unsigned *__restrict__ spans = nullptr;  // SPAN: the tables of the views flagged span-staged
     if (boxes_in != nullptr) {
         const uint4 hd = reinterpret_cast<const uint4 *>(boxes_in)[-1];
-        box_hdr_ok = hd.x == BOX_MAGIC && (int)hd.y == maxpix && (int)hd.z == V && (int)(hd.w & ~SPAN_FLAG) == TH;
-        span_ok = box_hdr_ok && (hd.w & SPAN_FLAG) && CK == 64 && WARP_HSCALAR && !WARP_STAGE_ALL;
+        // boxes made with span tables (SPAN_FLAG) are foreign to the span-free kernel
+        box_hdr_ok = hd.x == BOX_MAGIC && (int)hd.y == maxpix && (int)hd.z == V &&
+                     (int)(SPAN ? hd.w & ~SPAN_FLAG : hd.w) == TH;
+        if constexpr (SPAN) {
+            if (box_hdr_ok && (hd.w & SPAN_FLAG))
+                spans = reinterpret_cast<const unsigned *>(boxes_in + (int64_t)B * nt * V);
+        }
     }
     const uint2 *__restrict__ boxes = box_hdr_ok ? boxes_in : nullptr;
-    const unsigned *__restrict__ spans =
-        span_ok ? reinterpret_cast<const unsigned *>(boxes_in + (int64_t)B * nt * V) + WQ_WORDS : nullptr;
 
     // corner boxes of this tile for frame bb, lane v <-> view v, packed in two VGPRs (wave 0 computes them in
     // double, the others read them): lba = x0 | y0 << 16 | (!ok) << 31,  lbb = (x1 + 1) | (y1 + 1) << 16
@@ -1209,6 +1115,7 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
         return Box{(int)(a & 0xffffu), (int)((a >> 16) & 0x3fffu), (int)(c & 0xffffu) - 1, (int)(c >> 16) - 1};
     };
     auto ok_of = [&](int v) { return ((unsigned)__builtin_amdgcn_readlane((int)lba, v) >> 31) == 0u; };
+    // ---- span staging: called under `if constexpr (SPAN)` only ----
     auto span_of = [&](int v) {
         return spans != nullptr && ((unsigned)__builtin_amdgcn_readlane((int)lba, v) & 0x40000000u) != 0u;
     };
@@ -1274,7 +1181,7 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
     };
 
     {
-      for (int c0 = cfirst; c0 < C; c0 += 64) {
+      for (int c0 = 0; c0 < C; c0 += 64) {
         ccx = cx;
         ccy = cy;
         asm volatile("" : "+v"(ccx), "+v"(ccy));  // keep taps per chunk (no hoisting + spills)
@@ -1295,83 +1202,43 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
             }
             return u;
         };
-        if (WARP_STAGE_ALL) {
-            // ---- every live view's footprint at once: when all corner boxes apply and the images fit the pool
-            // together, they are staged back to back up front and the views are sampled with ONE wait + barrier
-            // per tile (instead of one per view) -- same taps, same view order, same arithmetic
-            int need = 0;  // lane v < V: view v's image bytes (0: empty view; huge: the corner box does not apply)
-            if (lane < V) {
-                const int x0 = (int)(lba & 0xffffu), y0 = (int)((lba >> 16) & 0x3fffu);
-                const int x1 = (int)(lbb & 0xffffu) - 1, y1 = (int)(lbb >> 16) - 1;
-                const int np = (x1 - x0 + 1) * (y1 - y0 + 1);
-                need = (lba >> 31) ? (1 << 26) : (x1 < 0 ? 0 : stage_bytes(np));
-            }
-            int tot = need;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
-            tot = __builtin_amdgcn_readfirstlane(tot);
-            if (tot <= pool) {
-                int off = 0;
-                for (int u = 0; u < V; ++u) {
-                    const Box bx = box_of(u);
-                    if (bx.x1 < 0) continue;
-                    const int w = bx.x1 - bx.x0 + 1, h = bx.y1 - bx.y0 + 1;
-                    dma(fb + (int64_t)u * sN, bx.x0, bx.y0, w, h, off);
-                    off += stage_bytes(w * h);
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();  // every image and the zero pixel
-                off = 0;
-                for (int u = 0; u < V; ++u) {
-                    const Box bx = box_of(u);
-                    if (bx.x1 < 0) {
-                        zero_view<MODE>(acc, u);
-                        continue;
-                    }
-                    const int w = bx.x1 - bx.x0 + 1;
-                    const Taps t = taps_of(u);
-                    if (__ballot(t.valid != 0) != 0ull && (!WARP_LANESKIP || t.valid))
-                        sample_view_pipe<MODE, CK, WARP_PIPE != 0>(acc, t, smem, off, bx.x0, bx.y0, w, zp, zp);
-                    else
-                        zero_view<MODE>(acc, u);
-                    off += stage_bytes(w * (bx.y1 - bx.y0 + 1));
-                }
-                if constexpr (NHWC) store_nhwc(c0, acc, md);
-                else if (inside) store_out(c0, acc, md);
-                if (c0 + 64 < C) __syncthreads();  // the next chunk re-stages the pool
-                continue;
-            }
-        }
         const int v_first = next_live(-1);
         auto peek_live = [&](int u) {  // next_live without the skipped views' max(acc, 0)
             ++u;
             while (u < V && !live(u)) ++u;
             return u;
         };
-        // prologue: DMA of the first live view (if its corner box applies and fits, or its spans do).  Span tables:
-        // spc = the current view's, spn = the next live view's (loaded during the view before, consumed after the
-        // end-of-view wait), both 0 for views without one.
+        // prologue: DMA of the first live view (if its corner box applies and fits, or its spans do)
         Box bn = box_of(v_first < V ? v_first : 0);
-        int offn = -1, bytesn = 0;  // the next image's LDS byte offset (-1: not staged ahead) and size
-        bool spsn = false;          // ... staged by spans
-        unsigned spc = 0u, spn = 0u;
+        int offn = -1;  // the next image's LDS byte offset (-1: not staged ahead)
+        // SPAN only: the next image's size and whether it is staged by spans; the span tables spc = the current
+        // view's, spn = the next live view's (loaded during the view before, consumed after the end-of-view wait),
+        // both 0 for views without one
+        [[maybe_unused]] int bytesn = 0;
+        [[maybe_unused]] bool spsn = false;
+        [[maybe_unused]] unsigned spc = 0u, spn = 0u;
         if (v_first < V) {
             const int npix = (bn.x1 - bn.x0 + 1) * (bn.y1 - bn.y0 + 1);
-            if (span_of(v_first)) {
-                spc = load_span(v_first);
-                asm volatile("" : "+v"(spc));  // its wait: nothing else in flight
-                int len, sxr, exc;
-                bytesn = span_scan(spc, bn.y1 - bn.y0 + 1, len, sxr, exc);
-                stage_span(fb + (int64_t)v_first * sN, bn.y0, bn.y1 - bn.y0 + 1, len, sxr, exc, 0);
+            if constexpr (SPAN) {
+                if (span_of(v_first)) {
+                    spc = load_span(v_first);
+                    asm volatile("" : "+v"(spc));  // its wait: nothing else in flight
+                    int len, sxr, exc;
+                    bytesn = span_scan(spc, bn.y1 - bn.y0 + 1, len, sxr, exc);
+                    stage_span(fb + (int64_t)v_first * sN, bn.y0, bn.y1 - bn.y0 + 1, len, sxr, exc, 0);
+                    offn = 0;
+                    spsn = true;
+                }
+            }
+            if (offn < 0 && ok_of(v_first) && bn.x1 >= 0 && npix <= maxpix) {
                 offn = 0;
-                spsn = true;
-            } else if (ok_of(v_first) && bn.x1 >= 0 && npix <= maxpix) {
-                offn = 0;
-                bytesn = ((npix * SL + 63) >> 6) * 1024;
+                if constexpr (SPAN) bytesn = ((npix * SL + 63) >> 6) * 1024;
                 dma(fb + (int64_t)v_first * sN, bn.x0, bn.y0, bn.x1 - bn.x0 + 1, bn.y1 - bn.y0 + 1, 0);
             }
-            const int vs = peek_live(v_first);
-            if (vs < V && span_of(vs)) spn = load_span(vs);
+            if constexpr (SPAN) {
+                const int vs = peek_live(v_first);
+                if (vs < V && span_of(vs)) spn = load_span(vs);
+            }
         }
         // the first live view's taps while its footprint lands (exact-bbox views reduce their taps first)
         Taps tf;
@@ -1382,15 +1249,16 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // zero pixel + image of the first live view
-        asm volatile("" : "+v"(spn));
+        if constexpr (SPAN) asm volatile("" : "+v"(spn));
         STAMP(2);
 
         int nview = 0;  // live views done (timing stamps)
         for (int v = v_first, vn; v < V; v = vn) {
             vn = next_live(v);
             Box bx = bn;
-            const int off = offn, bytesc = bytesn;
-            const bool spsc = spsn;
+            const int off = offn;
+            [[maybe_unused]] const int bytesc = bytesn;  // SPAN only, as bytesn / spsn: this view's image
+            [[maybe_unused]] const bool spsc = spsn;
             const float *f = fb + (int64_t)v * sN;
             Taps t;
             bool have_t = false;
@@ -1410,25 +1278,27 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
             const bool empty = bx.x1 < 0;
             const int bw = bx.x1 - bx.x0 + 1, bh = bx.y1 - bx.y0 + 1;
             bool done = empty;
-            if (!done && off < 0 && span_of(v)) {
-                // ---- synchronous span staging (no room was left beside the previous image) ----
-                int len, sxr, exc;
-                span_scan(spc, bh, len, sxr, exc);
-                stage_span(f, bx.y0, bh, len, sxr, exc, 0);
-                if (!have_t) {
-                    t = taps_of(v);
-                    have_t = true;
+            if constexpr (SPAN) {
+                if (!done && off < 0 && span_of(v)) {
+                    // ---- synchronous span staging (no room was left beside the previous image) ----
+                    int len, sxr, exc;
+                    span_scan(spc, bh, len, sxr, exc);
+                    stage_span(f, bx.y0, bh, len, sxr, exc, 0);
+                    if (!have_t) {
+                        t = taps_of(v);
+                        have_t = true;
+                    }
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __syncthreads();
+                    if (__ballot(t.valid != 0) != 0ull && (!WARP_LANESKIP || t.valid)) {
+                        int pb, pbs;
+                        span_addr(t, 0, bx.y0, pb, pbs);
+                        sample_pipe_at<MODE, CK, WARP_PIPE != 0>(acc, t, smem, pb, pbs, zp, zp);
+                    } else
+                        zero_view<MODE>(acc, v);
+                    done = true;
+                    __syncthreads();  // the pool is free again
                 }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (__ballot(t.valid != 0) != 0ull && (!WARP_LANESKIP || t.valid)) {
-                    int pb, pbs;
-                    span_addr(t, 0, bx.y0, pb, pbs);
-                    sample_pipe_at<MODE, CK, WARP_PIPE != 0>(acc, t, smem, pb, pbs, zp, zp);
-                } else
-                    zero_view<MODE>(acc, v);
-                done = true;
-                __syncthreads();  // the pool is free again
             }
             if (!done && off < 0) {
                 // ---- synchronous staging, overlapping blocks if larger than the pool ----
@@ -1474,57 +1344,56 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
                 __syncthreads();  // every wave is done with the staged blocks before DMA(v+1) reuses the pool
             }
             // ---- look ahead: DMA of the next live view beside the live image of view v ----
-            unsigned spnn = 0u;  // the span table of the live view after vn
+            [[maybe_unused]] unsigned spnn = 0u;  // SPAN: the span table of the live view after vn
             if (vn < V) {
                 bn = box_of(vn);
                 offn = -1;
-                spsn = false;
                 const int npix = (bn.x1 - bn.x0 + 1) * (bn.y1 - bn.y0 + 1);
-                const bool sp = span_of(vn);
+                bool sp = false;  // vn is staged by spans
+                if constexpr (SPAN) {
+                    spsn = false;
+                    sp = span_of(vn);
+                }
                 if (ok_of(vn) && bn.x1 >= 0 && (sp || npix <= maxpix)) {
                     // consecutive images anchor at opposite ends of the pool: they coexist
                     // whenever their sizes add up to at most the pool
-                    int len = 0, sxr = 0, exc = 0;
-                    const int need = sp ? span_scan(spn, bn.y1 - bn.y0 + 1, len, sxr, exc)
-                                        : ((npix * SL + 63) >> 6) * 1024;
+                    [[maybe_unused]] int len = 0, sxr = 0, exc = 0;
+                    int need = ((npix * SL + 63) >> 6) * 1024, cur = ((bw * bh * SL + 63) >> 6) * 1024;
+                    if constexpr (SPAN) {
+                        if (sp) need = span_scan(spn, bn.y1 - bn.y0 + 1, len, sxr, exc);
+                        cur = bytesc;
+                    }
                     if (done || off < 0) offn = 0;
                     else if (off == 0) {
-                        if (bytesc + need <= pool) offn = pool - need;
+                        if (cur + need <= pool) offn = pool - need;
                     } else if (need <= off) offn = 0;
                     if (offn >= 0) {
-                        if (sp) stage_span(fb + (int64_t)vn * sN, bn.y0, bn.y1 - bn.y0 + 1, len, sxr, exc, offn);
-                        else dma(fb + (int64_t)vn * sN, bn.x0, bn.y0, bn.x1 - bn.x0 + 1, bn.y1 - bn.y0 + 1, offn);
-                        bytesn = need;
-                        spsn = sp;
+                        if constexpr (SPAN) {
+                            if (sp) stage_span(fb + (int64_t)vn * sN, bn.y0, bn.y1 - bn.y0 + 1, len, sxr, exc, offn);
+                            bytesn = need;
+                            spsn = sp;
+                        }
+                        if (!sp) dma(fb + (int64_t)vn * sN, bn.x0, bn.y0, bn.x1 - bn.x0 + 1, bn.y1 - bn.y0 + 1, offn);
                     }
                 }
-                const int vnn = peek_live(vn);
-                if (vnn < V && span_of(vnn)) spnn = load_span(vnn);
+                if constexpr (SPAN) {
+                    const int vnn = peek_live(vn);
+                    if (vnn < V && span_of(vnn)) spnn = load_span(vnn);
+                }
             }
             // ---- sample view v from its prefetched image ------------------------------
             if (!done) {
                 if (!have_t) t = taps_of(v);
                 STAMP_VIEW(nview, 0);
-                int pb, pbs;  // the taps' LDS pixels
-                if (spsc) {
-                    span_addr(t, off, bx.y0, pb, pbs);
-                } else {
-                    pb = off + ((t.y0 - bx.y0) * bw + (t.x0 - bx.x0)) * PS;
-                    pbs = pb + bw * PS;
+                int pb = off + ((t.y0 - bx.y0) * bw + (t.x0 - bx.x0)) * PS, pbs = pb + bw * PS;  // the taps' LDS pixels
+                if constexpr (SPAN) {
+                    if (spsc) span_addr(t, off, bx.y0, pb, pbs);
                 }
                 if (WARP_ABLATE & 4) acc[0] += t.w[0] * t.w[3] + (float)(t.x0 + t.y0 + (int)t.valid);
                 else if (__ballot(t.valid != 0) != 0ull) {
                     // WARP_LANESKIP: lanes without a valid tap leave the LDS reads to the others (their sample is
                     // +0: acc + 0 == acc exactly, max(acc, 0) for the max mode)
-                    if (WARP_TAPS_AHEAD && vn < V && ok_of(vn)) {
-                        // the next view's taps inside this view's sampling, by every lane (a lane without a valid tap
-                        // reads the zero pixel: its sample is +0, i.e. acc + 0 == acc, or max(acc, +0) -- what the
-                        // lane skip gives)
-                        sample_pipe_at<MODE, CK, WARP_PIPE != 0, WARP_TAPS_AHEAD - 2>(
-                            acc, t, smem, pb, pbs, zp, zp, [&]() { tf = taps_of(vn); });
-                        if (WARP_TAPS_AHEAD == 1) tf = taps_of(vn);  // after the sampling, before the DMA wait
-                        have_f = true;
-                    } else if (!WARP_LANESKIP || t.valid)
+                    if (!WARP_LANESKIP || t.valid)
                         sample_pipe_at<MODE, CK, WARP_PIPE != 0>(acc, t, smem, pb, pbs, zp, zp);
                     else zero_view<MODE>(acc, v);
                 } else zero_view<MODE>(acc, v);
@@ -1534,9 +1403,11 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
             STAMP_VIEW(nview, 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of view v+1 landed
             __syncthreads();  // all of it landed; image of view v and red[] are free
-            spc = spn;
-            spn = spnn;
-            asm volatile("" : "+v"(spn));  // landed with the DMA
+            if constexpr (SPAN) {
+                spc = spn;
+                spn = spnn;
+                asm volatile("" : "+v"(spn));  // landed with the DMA
+            }
             STAMP_VIEW(nview, 2);
             ++nview;
         }
@@ -1551,292 +1422,19 @@ __global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_v2(const float *__rest
     }
 }
 
-// -------------------------------------------------------------------------
-// fused warp + sum / mean, persistent (k_warp_fuse_p; BEV_TUNE_WARP_PERSIST 1 / 2, an A/B option: measured SLOWER)
-// -------------------------------------------------------------------------
-// Measured (r06w-r06y, tools/warp_persist_ab.py, interleaved, us per launch): bench 7 cams B = 2 per-tile 135-137,
-// persistent 8 queues 150-154, 1 queue 144-146 (8 queues + stealing from the next queue at the tail: 194);
-// K5 16 cams 4K 218-224 vs 245-252.  Bit-identical in every form (test_fused_persistent_equals_per_tile_kernel).
-// Why it loses: the in-order vmcnt hides the first DMA behind the previous item's stores (vmcnt(63)), but EVERY
-// later DMA wait of the item (the end of each view) also waits for those 64 stores, so their drain lands on the
-// item's first view; a workgroup of v2 simply ends after its stores and the drain overlaps its successor's start.
-// k_warp_fuse_v2's per-item work (one frame x 16 x 16 BEV tile, 64 channels: taps, footprint DMA one view ahead,
-// LDS sampling, view order from +0, the mean by the same division) in CUs x OCC resident workgroups that pull items
-// from work queues instead of one workgroup per item.  What the loop buys (v2's s_memtime timeline: per workgroup
-// ~34 k cycles = prologue 1.6 k + first view's DMA 4.2 k + views 25.2 k + stores 3.1 k, and 2 k from a workgroup's
-// end to its successor's start): the next item's boxes and first-view DMA are issued BEFORE this item's output
-// stores, so that DMA lands while the 64 store instructions issue and the next item's taps are computed; the wait
-// before its first sampling is `vmcnt(63)` (every vector-memory op counts in issue order, MI355X_MICROARCH.md
-// §vmcnt: with >= 64 stores younger than the DMA, <= 63 outstanding means the DMA is done, the stores need not be),
-// and the barrier after it a raw s_barrier (no fence drain of the stores).  No workgroup launch gap.
-// Queues: q = blockIdx % 8 (the XCD under round-robin dispatch) owns the contiguous item range
-// [total q / 8, total (q + 1) / 8) (item = frame x tiles + tile): an XCD walks neighbouring tiles, whose footprints
-// share source pixels in its L2.  A workgroup's first item is static (lo + blockIdx / 8), the next ones a ticket
-// (atomicAdd on the queue word, fetched at the start of the current item and read after its views).  The queue
-// words live after the boxes in the workspace: zeroed by k_warp_boxes and reset by the last workgroup to finish
-// (a finished-count word), so every launch starts from zero.  Each workgroup exits once its queue is drained --
-// no inter-workgroup waits, so residency is not needed for progress.
-// Same per-cell arithmetic and view order as v2 => bit-identical output.
-
-template <int MODE, int OCC, bool CHUNK>
-__global__ __launch_bounds__(FT_NT, OCC) void k_warp_fuse_p(const float *__restrict__ feats, int64_t sN, int64_t sH,
-                                                         int64_t sW, const float *__restrict__ Hmat,
-                                                         const float *__restrict__ xs, const float *__restrict__ ys,
-                                                         int B, int V, int C, int Hf, int Wf, float sx, float sy,
-                                                         int Hb, int Wb, float *__restrict__ out, int pool,
-                                                         const uint2 *__restrict__ boxes_in, int rpr,
-                                                         unsigned *__restrict__ queue, int nqs) {
-    static_assert(MODE != BEV_FUSE_MAX, "sum / mean");
-    constexpr int NW = FT_NT / 64, TH = 16, TW = FT_NT / TH, CK = 64, SL = V2_SL, PS = SL * 16;
-    static_assert(WARP_CK == 64, "one workgroup per (tile, frame)");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int zp = pool;
-    int *red = reinterpret_cast<int *>(smem + pool + 256);
-    int *slot = reinterpret_cast<int *>(smem + pool + 256 + 4 * NW * sizeof(int));  // the next ticket (htab area)
-    const int maxpix = pool / PS - 4;
-    const int ntx = (Wb + TW - 1) / TW, nty = (Hb + TH - 1) / TH, nt = ntx * nty;
-    const int total = nt * B;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tr, tc;
-    tile_cell<TH>(lane, wave, tr, tc);
-    const int qi = (int)(blockIdx.x % (unsigned)nqs);
-    const int nq = (int)(gridDim.x / (unsigned)nqs);  // workgroups per queue (gridDim.x % nqs == 0)
-    const int lo = (int)((int64_t)total * qi / nqs), hi = (int)((int64_t)total * (qi + 1) / nqs);
-    bool hdr_ok = false;
-    {
-        const uint4 hd = reinterpret_cast<const uint4 *>(boxes_in)[-1];
-        hdr_ok = hd.x == BOX_MAGIC && (int)hd.y == maxpix && (int)hd.z == V && (int)hd.w == TH;
-    }
-    const Grid grid = make_grid(Hf, Wf);
-    const MeanDiv md = mean_div_of(V);
-    if (tid < 16) *(float4 *)(smem + zp + tid * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
-    const size_t plane = (size_t)Hb * Wb;
-    const size_t oplane = CHUNK ? (size_t)rpr * Wb : plane;
-    auto dma = [&](const float *fp, int x0, int y0, int w, int h, int o) {
-        dma_block<SL>(fp, (int)sH, (int)sW, x0, y0, w, w * h, smem, o, wave, lane, NW);
-    };
-
-    // the item being set up: frame, tile origin, this lane's cell, its centre, the boxes of its views
-    int b = 0, tyb = 0, txb = 0, ci = 0, cj = 0;
-    bool inside = false;
-    float cx = 0.f, cy = 0.f;
-    unsigned lba = 0, lbb = 0;
-    auto load_item = [&](int it) {
-        b = it / nt;
-        const int tile = it - b * nt;
-        tyb = tile / ntx;
-        txb = tile - tyb * ntx;
-        ci = tyb * TH + tr;
-        cj = txb * TW + tc;
-        inside = (ci < Hb) && (cj < Wb);
-        cx = xs[inside ? cj : 0];
-        cy = ys[inside ? ci : 0];
-        if (hdr_ok) {
-            const uint2 bx = lane < V ? boxes_in[((int64_t)b * nt + tile) * V + lane] : make_uint2(0u, 0u);
-            lba = bx.x;
-            lbb = bx.y;
-        } else {  // boxes made for another pool / V / tiling: every view by the exact per-cell reduction
-            lba = lane < V ? 0x80000000u : 0u;
-            lbb = 0u;
-        }
-    };
-    auto box_of = [&](int v) {
-        const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)lba, v);
-        const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)lbb, v);
-        return Box{(int)(a & 0xffffu), (int)((a >> 16) & 0x7fffu), (int)(c & 0xffffu) - 1, (int)(c >> 16) - 1};
-    };
-    auto ok_of = [&](int v) { return ((unsigned)__builtin_amdgcn_readlane((int)lba, v) >> 31) == 0u; };
-    auto live = [&](int u) { return !ok_of(u) || box_of(u).x1 >= 0; };
-    auto next_live = [&](int u) {  // sum / mean: views with an empty box contribute +0 -- skipped exactly
-        ++u;
-        while (u < V && !live(u)) ++u;
-        return u;
-    };
-    float ccx = 0.f, ccy = 0.f;
-    auto taps_of = [&](int v, bool in) {
-        float h[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) h[k] = Hmat[__builtin_amdgcn_readfirstlane((b * V + v) * 9) + k];
-        float ix, iy;
-        cell_ixy(h, ccx, ccy, grid, sx, sy, ix, iy);
-        Taps t = taps_from_ixy(ix, iy, grid);
-        if (!in) t.valid = 0;
-        return t;
-    };
-    // the first live view of the item just loaded, its DMA issued now (offn = 0) when its corner box fits the pool
-    int v_first = V, offn = -1;
-    Box bn{0, 0, -1, -1};
-    auto first_dma = [&]() {
-        v_first = next_live(-1);
-        bn = box_of(v_first < V ? v_first : 0);
-        offn = -1;
-        if (v_first < V) {
-            const int npix = (bn.x1 - bn.x0 + 1) * (bn.y1 - bn.y0 + 1);
-            if (ok_of(v_first) && bn.x1 >= 0 && npix <= maxpix) {
-                offn = 0;
-                dma(feats + (int64_t)(b * V + v_first) * sN, bn.x0, bn.y0, bn.x1 - bn.x0 + 1, bn.y1 - bn.y0 + 1, 0);
-            }
-        }
-    };
-
-    int item = lo + (int)(blockIdx.x / (unsigned)nqs);
-    if (item < hi) {
-        load_item(item);
-        first_dma();
-    }
-    bool stores_out = false;  // this wave issued the previous item's 64 output stores after the current first DMA
-    while (item < hi) {
-        int tkt = 0;
-        if (tid == 0) tkt = (int)atomicAdd(&queue[qi], 1u);  // the next ticket, read after this item's views
-        const int bi = b, ii = ci, jj = cj;
-        const bool in = inside;
-        ccx = cx;
-        ccy = cy;
-        asm volatile("" : "+v"(ccx), "+v"(ccy));  // keep the taps per item (no hoisting + spills)
-        float acc[CK];
-#pragma unroll
-        for (int k = 0; k < CK; ++k) acc[k] = 0.0f;
-        const float *fb = feats + (int64_t)(bi * V) * sN;
-        Taps tf;
-        bool have_f = false;
-        if (v_first < V && ok_of(v_first)) {
-            tf = taps_of(v_first, in);
-            have_f = true;
-        }
-        // the first live view's image (and the zero pixel); the previous item's stores may still be in flight
-        if (stores_out) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        for (int v = v_first, vn; v < V; v = vn) {
-            vn = next_live(v);
-            Box bx = bn;
-            const int off = offn;
-            const float *f = fb + (int64_t)v * sN;
-            Taps t;
-            bool have_t = false;
-            if (have_f) {
-                t = tf;
-                have_t = true;
-                have_f = false;
-            }
-            if (!ok_of(v)) {  // exact footprint by per-cell reduction (horizon tiles); staged synchronously
-                t = taps_of(v, in);
-                have_t = true;
-                put_box<NW>(red, wave_box(t), wave, lane);
-                __syncthreads();
-                bx = get_box<NW>(red);
-            }
-            const bool empty = bx.x1 < 0;
-            const int bw = bx.x1 - bx.x0 + 1, bh = bx.y1 - bx.y0 + 1;
-            bool done = empty;
-            if (!done && off < 0) {  // synchronous staging, overlapping blocks if larger than the pool (as v2)
-                int wb = bw, hb = bh, nbx = 1, nby = 1;
-                if (bw * bh > maxpix) {
-                    wb = (2 * bw <= maxpix) ? bw : maxpix / 2;
-                    hb = min(bh, maxpix / wb);
-                    nbx = (wb >= bw) ? 1 : (bw - 2) / (wb - 1) + 1;
-                    nby = (hb >= bh) ? 1 : (bh - 2) / (hb - 1) + 1;
-                }
-                const bool single = (nbx == 1) && (nby == 1);
-                if (single) dma(f, bx.x0, bx.y0, bw, bh, 0);
-                if (!have_t) {
-                    t = taps_of(v, in);
-                    have_t = true;
-                }
-                int mkx = 0, mky = 0;
-                if (!single && t.valid) {
-                    const int xlo = (t.valid & 5) ? t.x0 : t.x0 + 1, ylo = (t.valid & 3) ? t.y0 : t.y0 + 1;
-                    mkx = (nbx == 1) ? 0 : min((xlo - bx.x0) / (wb - 1), nbx - 1);
-                    mky = (nby == 1) ? 0 : min((ylo - bx.y0) / (hb - 1), nby - 1);
-                }
-                const bool wave_any = __ballot(t.valid != 0) != 0ull;
-                for (int ky = 0; ky < nby; ++ky)
-                    for (int kx = 0; kx < nbx; ++kx) {
-                        const int sx0 = bx.x0 + kx * (wb - 1), sy0 = bx.y0 + ky * (hb - 1);
-                        const int sbw = min(wb, bx.x1 - sx0 + 1), sbh = min(hb, bx.y1 - sy0 + 1);
-                        if (!single) {
-                            __syncthreads();
-                            dma(f, sx0, sy0, sbw, sbh, 0);
-                        }
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        __syncthreads();
-                        const bool mine = single ? true : (t.valid != 0 && mkx == kx && mky == ky);
-                        const bool go = single ? wave_any : (__ballot(mine) != 0ull);
-                        if (go) sample_view<MODE, 1, CK>(acc, t, mine, v, smem, 0, sx0, sy0, sbw, zp);
-                    }
-                done = true;
-                __syncthreads();
-            }
-            if (vn < V) {  // look ahead: DMA of the next live view beside the live image of view v
-                bn = box_of(vn);
-                offn = -1;
-                const int npix = (bn.x1 - bn.x0 + 1) * (bn.y1 - bn.y0 + 1);
-                if (ok_of(vn) && bn.x1 >= 0 && npix <= maxpix) {
-                    const int need = ((npix * SL + 63) >> 6) * 1024;
-                    if (done || off < 0) offn = 0;
-                    else if (off == 0) {
-                        if (((bw * bh * SL + 63) >> 6) * 1024 + need <= pool) offn = pool - need;
-                    } else if (need <= off) offn = 0;
-                    if (offn >= 0) dma(fb + (int64_t)vn * sN, bn.x0, bn.y0, bn.x1 - bn.x0 + 1, bn.y1 - bn.y0 + 1, offn);
-                }
-            }
-            if (!done) {
-                if (!have_t) t = taps_of(v, in);
-                if (__ballot(t.valid != 0) != 0ull && (!WARP_LANESKIP || t.valid))
-                    sample_view_pipe<MODE, CK, WARP_PIPE != 0>(acc, t, smem, off, bx.x0, bx.y0, bw, zp, zp);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of view v+1 landed
-            __syncthreads();  // all of it landed; image of view v and red[] are free
-        }
-        // the next item: its ticket, boxes and first-view DMA before this item's stores (the pool is free: every
-        // view of this item ended with a barrier after its last LDS read)
-        if (tid == 0) *slot = tkt;
-        __syncthreads();
-        const int nxt = lo + nq + __builtin_amdgcn_readfirstlane(*slot);
-        if (nxt < hi) {
-            load_item(nxt);
-            first_dma();
-        }
-        item = nxt;
-        if (in) {
-            if (!CHUNK) {
-                store_chunk(out + (size_t)bi * C * plane, plane, (ii * Wb + jj) * (int)sizeof(float), acc, MODE, md,
-                            (uint32_t)(plane * CK * sizeof(float)));
-            } else {
-                const int ck = ii / rpr;
-                const int ovoff = (int)(((size_t)ck * B * C * oplane + (size_t)(ii - ck * rpr) * Wb + jj) * sizeof(float));
-                const size_t orange = (size_t)((Hb + rpr - 1) / rpr) * B * C * oplane * sizeof(float);
-                store_chunk(out + (size_t)bi * C * oplane, oplane, ovoff, acc, MODE, md,
-                            out_range(orange, (size_t)bi * C * oplane));
-            }
-        }
-        stores_out = __ballot(in) != 0ull;
-    }
-    // queue bookkeeping: the last workgroup to finish resets the words for the next launch
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned d = atomicAdd(&queue[8], 1u);
-        if (d == gridDim.x - 1) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) atomicExch(&queue[k], 0u);
-        }
-    }
-}
-
-template <int TH, int TW = FT_NT / TH>
+template <int TH>
 __global__ __launch_bounds__(256) void k_warp_boxes(const float *__restrict__ Hmat, const float *__restrict__ xs,
                                                     const float *__restrict__ ys, int V, int Hf, int Wf, float sx,
                                                     float sy, int Hb, int Wb, int maxpix, int nty,
-                                                    uint2 *__restrict__ boxes, unsigned *__restrict__ queue,
-                                                    unsigned *__restrict__ spans, int span_pct) {
+                                                    uint2 *__restrict__ boxes, unsigned *__restrict__ spans,
+                                                    int span_pct) {
+    constexpr int TW = FT_NT / TH;
     const int ntx = (Wb + TW - 1) / TW, nt = ntx * nty;  // nty >= ceil(Hb / TH) box-tile rows (extra rows: empty)
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
     if (t == 0 && b == 0)
         reinterpret_cast<uint4 *>(boxes)[-1] =
             make_uint4(BOX_MAGIC, (unsigned)maxpix, (unsigned)V, (unsigned)TH | (spans ? SPAN_FLAG : 0u));
-    if (queue != nullptr && b == 0 && t < WQ_WORDS) queue[t] = 0u;  // k_warp_fuse_p's work queues start at zero
     if (t >= (int64_t)nt * V) return;
     const int tile = (int)(t / V), v = (int)(t - (int64_t)tile * V);
     const int tyb = tile / ntx, txb = tile - tyb * ntx;
@@ -2212,10 +1810,6 @@ int g_warp_pool_kb = 0;  // BEV_TUNE_WARP_POOL_KB: LDS image pool / ring per wor
 int g_warp_kernel = 0;   // BEV_TUNE_WARP_KERNEL: 0 default (= 2), 1 register-staged k_warp_fuse, 2 per-view LDS-DMA
                          // k_warp_fuse_v2, 3 DPP-row k_warp_fuse_v3 (sum / mean with a workspace)
 int g_warp_bwd_pool = 0; // BEV_TUNE_WARP_BWD_POOL: backward LDS image in floats, 0 = WARP_BWD_POOL_MAX
-// BEV_TUNE_WARP_PERSIST: 0 (default) = k_warp_fuse_v2; 1 = k_warp_fuse_p with 8 work queues, 2 = with one queue.
-// r06x A/B (tools/warp_persist_ab.py, us per launch, bench / K5): per-tile 136.2 / 220.0, persistent 8 queues
-// 150.2 / 247.6, 1 queue 145.6 / 245.7 -- slower: see k_warp_fuse_p (the store drain the next DMA waits behind).
-int g_warp_persist = 0;
 int g_warp_span_pct = WARP_SPAN_PCT;  // BEV_TUNE_WARP_SPAN: span staging threshold in percent, 0 = off
 // BEV_TUNE_WARP_TILE_BAND: fused warp v2 tile order, 1 = row-major, n = bands of n tile rows walked column by column,
 // 0 = automatic: bands of 4 for >= 12 views (read-heavy: the 16-camera 4K rig's warp 228.9 -> 220.5 us and its reads
@@ -2224,18 +1818,6 @@ int g_warp_span_pct = WARP_SPAN_PCT;  // BEV_TUNE_WARP_SPAN: span staging thresh
 int g_warp_tile_band = 0;
 
 constexpr int FUSE_LDS_BYTES = 60 * 1024;  // register-staged kernel's footprint image
-
-int cu_count() {
-    static int cache[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (cache[dev] == 0) {
-        int c = 0;
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
-        cache[dev] = c;
-    }
-    return cache[dev];
-}
 
 template <int CK, bool VEC>
 int launch_fuse(const float *feats, int64_t sN, int64_t sC, int64_t sH, int64_t sW, const float *Hmat, const float *xs,
@@ -2276,68 +1858,8 @@ int launch_fuse_ck(const float *feats, int64_t sN, int64_t sC, int64_t sH, int64
 #ifndef WARP_TILE_H
 #define WARP_TILE_H 16  // fused-warp tile: 16 x 16 (default) or 8 x 32 cells (A/B builds)
 #endif
-#ifndef WARP_OCC
-#define WARP_OCC 3   // workgroups per CU the default (mean / sum) kernel is compiled and sized for
-#endif
 constexpr int V2_FIXED = 256 + 4 * (FT_NT / 64) * (int)sizeof(int) + V2_MAXV * 9 * (int)sizeof(float) +
                          (2 * V2_MAXV + 4) * (int)sizeof(unsigned);  // zero pixel, red, htab, btab
-
-// k_warp_boxes' span tables (after the queue words), or none: span staging off (knob 0), or boxes for a kernel that
-// does not read them (the persistent kernel; v2 builds with 32-channel workgroups, staging everything up front or
-// the LDS homography prologue)
-inline unsigned *span_tables(unsigned *queue, bool persist) {
-    if (!queue || persist || g_warp_span_pct <= 0 || WARP_CK != 64 || WARP_STAGE_ALL || !WARP_HSCALAR) return nullptr;
-    return queue + WQ_WORDS;
-}
-
-template <int OCC>
-int launch_fuse_v2_occ(const float *feats, int64_t sN, int64_t sH, int64_t sW, const float *Hmat, const float *xs,
-                       const float *ys, int B, int V, int C, int Hf, int Wf, float sx, float sy, int Hb, int Wb,
-                       int mode, float *out, hipStream_t st, int pool, uint2 *boxes, bool boxes_ready, int rpr) {
-    constexpr int TH = WARP_TILE_H, TW = FT_NT / TH;
-    const int ntiles = ((Wb + TW - 1) / TW) * ((Hb + TH - 1) / TH);
-    dim3 grid(ntiles, B * V2_SPLIT), block(FT_NT);
-    const size_t lds = (size_t)pool + V2_FIXED;
-    if (!WARP_HSCALAR) boxes = nullptr;  // the in-kernel prologue (LDS homographies)
-    unsigned *queue = boxes ? reinterpret_cast<unsigned *>(boxes + (int64_t)B * ntiles * V) : nullptr;
-    const bool nhwc = rpr == 0;          // channels-last output (bev_ipm_warp_fuse_nhwc_f32)
-    const bool ck = !nhwc && rpr < Hb;  // rank-chunk-major output (camera-shard partials)
-    const bool persist = g_warp_persist && boxes && !nhwc && C == 64 && mode != BEV_FUSE_MAX && TH == 16 &&
-                         WARP_CK == 64 && !WARP_STAGE_ALL && !WARP_TAPS_AHEAD;
-    if (boxes && !boxes_ready) {  // else bev_ipm_warp_fuse_boxes_f32 wrote them (same geometry, pool and knobs)
-        const int maxpix = pool / (V2_SL * 16) - 4;  // the kernel's own pool test
-        hipLaunchKernelGGL((k_warp_boxes<TH>), dim3((unsigned)(((int64_t)ntiles * V + 255) / 256), B), dim3(256), 0,
-                           st, Hmat, xs, ys, V, Hf, Wf, sx, sy, Hb, Wb, maxpix, (Hb + TH - 1) / TH, boxes, queue,
-                           span_tables(queue, persist), g_warp_span_pct);
-    }
-    if (persist) {
-        // persistent: OCC resident workgroups per CU, a multiple of 8 (one work queue per XCD)
-        const int nq = (cu_count() * OCC + 7) / 8;
-        const dim3 pgrid((unsigned)(8 * nq)), pblock(FT_NT);
-        auto gop = [&](auto kern) {
-            hipLaunchKernelGGL(kern, pgrid, pblock, lds, st, feats, sN, sH, sW, Hmat, xs, ys, B, V, C, Hf, Wf, sx, sy,
-                               Hb, Wb, out, pool, boxes, rpr, queue, g_warp_persist == 2 ? 1 : 8);
-        };
-        if (mode == BEV_FUSE_SUM) ck ? gop(k_warp_fuse_p<BEV_FUSE_SUM, OCC, true>) : gop(k_warp_fuse_p<BEV_FUSE_SUM, OCC, false>);
-        else ck ? gop(k_warp_fuse_p<BEV_FUSE_MEAN, OCC, true>) : gop(k_warp_fuse_p<BEV_FUSE_MEAN, OCC, false>);
-        return last();
-    }
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, block, lds, st, feats, sN, sH, sW, Hmat, xs, ys, B, V, C, Hf, Wf, sx, sy, Hb, Wb,
-                           out, pool, boxes, rpr, g_warp_tile_band > 0 ? g_warp_tile_band : (V >= 12 ? 4 : 1));
-    };
-    if (nhwc) {
-        if (mode == BEV_FUSE_SUM) go(k_warp_fuse_v2<BEV_FUSE_SUM, OCC, TH, false, true>);
-        else if (mode == BEV_FUSE_MEAN) go(k_warp_fuse_v2<BEV_FUSE_MEAN, OCC, TH, false, true>);
-        else go(k_warp_fuse_v2<BEV_FUSE_MAX, OCC, TH, false, true>);
-    } else if (mode == BEV_FUSE_SUM)
-        ck ? go(k_warp_fuse_v2<BEV_FUSE_SUM, OCC, TH, true>) : go(k_warp_fuse_v2<BEV_FUSE_SUM, OCC, TH, false>);
-    else if (mode == BEV_FUSE_MEAN)
-        ck ? go(k_warp_fuse_v2<BEV_FUSE_MEAN, OCC, TH, true>) : go(k_warp_fuse_v2<BEV_FUSE_MEAN, OCC, TH, false>);
-    else
-        ck ? go(k_warp_fuse_v2<BEV_FUSE_MAX, OCC, TH, true>) : go(k_warp_fuse_v2<BEV_FUSE_MAX, OCC, TH, false>);
-    return last();
-}
 
 // V for which k_warp_fuse_v3's fp32 mean division (w3_div) is exact for every input but -0: bit V - 1, from the
 // exhaustive check tools/verify_div_markstein_fix.c (other V divide through double, div_rcp).
@@ -2349,8 +1871,8 @@ int launch_fuse_v3(const float *feats, int64_t sN, int64_t sH, int64_t sW, const
     const int ntx = (Wb + 15) / 16, nty = (Hb + 15) / 16, ntiles = ntx * nty;
     // 3 workgroups per CU: pool + zero pixel <= 160 KiB / 3
     const int pool = g_warp_pool_kb ? g_warp_pool_kb * 1024 : ((163840 / 3 - 256 - 64) & ~1023);
-    hipLaunchKernelGGL((k_warp_boxes<16, 16>), dim3((unsigned)(((int64_t)ntiles * V + 255) / 256), B), dim3(256), 0,
-                       st, Hmat, xs, ys, V, Hf, Wf, sx, sy, Hb, Wb, pool / W3_PIX, nty, boxes, nullptr, nullptr, 0);
+    hipLaunchKernelGGL((k_warp_boxes<16>), dim3((unsigned)(((int64_t)ntiles * V + 255) / 256), B), dim3(256), 0,
+                       st, Hmat, xs, ys, V, Hf, Wf, sx, sy, Hb, Wb, pool / W3_PIX, nty, boxes, nullptr, 0);
     const int fastdiv = (V >= 1 && V <= 64 && ((W3_FASTDIV_V >> (V - 1)) & 1)) ? 1 : 0;
     const size_t lds = (size_t)pool + 256;
     if (mode == BEV_FUSE_SUM)
@@ -2370,14 +1892,49 @@ inline int v2_pool_bytes(int mode) {
     return kb ? kb * 1024 : (pool3 < 49 * 1024 ? pool3 : 49 * 1024);
 }
 
-inline int launch_fuse_v2(const float *feats, int64_t sN, int64_t sH, int64_t sW, const float *Hmat,
-                          const float *xs, const float *ys, int B, int V, int C, int Hf, int Wf, float sx, float sy,
-                          int Hb, int Wb, int mode, float *out, hipStream_t st, uint2 *boxes, bool boxes_ready, int rpr) {
-    if (mode == BEV_FUSE_MAX)  // MAX's extra live state spills at 3 workgroups per CU
-        return launch_fuse_v2_occ<2>(feats, sN, sH, sW, Hmat, xs, ys, B, V, C, Hf, Wf, sx, sy, Hb, Wb, mode, out, st,
-                                     v2_pool_bytes(mode), boxes, boxes_ready, rpr);
-    return launch_fuse_v2_occ<WARP_OCC>(feats, sN, sH, sW, Hmat, xs, ys, B, V, C, Hf, Wf, sx, sy, Hb, Wb, mode, out,
-                                        st, v2_pool_bytes(mode), boxes, boxes_ready, rpr);
+// k_warp_boxes' span tables (after the nboxes boxes), or none: no box workspace, span staging off (knob 0), or a
+// build whose fused kernel does not read the boxes (the LDS homography prologue)
+inline unsigned *span_tables(uint2 *boxes, int64_t nboxes) {
+    if (!boxes || g_warp_span_pct <= 0 || !WARP_HSCALAR) return nullptr;
+    return reinterpret_cast<unsigned *>(boxes + nboxes);
+}
+
+int launch_fuse_v2(const float *feats, int64_t sN, int64_t sH, int64_t sW, const float *Hmat, const float *xs,
+                   const float *ys, int B, int V, int C, int Hf, int Wf, float sx, float sy, int Hb, int Wb, int mode,
+                   float *out, hipStream_t st, uint2 *boxes, bool boxes_ready, int rpr) {
+    constexpr int TH = WARP_TILE_H, TW = FT_NT / TH;
+    const int ntiles = ((Wb + TW - 1) / TW) * ((Hb + TH - 1) / TH);
+    dim3 grid(ntiles, B), block(FT_NT);
+    const int pool = v2_pool_bytes(mode);
+    const size_t lds = (size_t)pool + V2_FIXED;
+    if (!WARP_HSCALAR) boxes = nullptr;  // the in-kernel prologue (LDS homographies)
+    unsigned *spans = span_tables(boxes, (int64_t)B * ntiles * V);
+    const bool nhwc = rpr == 0;          // channels-last output (bev_ipm_warp_fuse_nhwc_f32)
+    const bool ck = !nhwc && rpr < Hb;  // rank-chunk-major output (camera-shard partials)
+    if (boxes && !boxes_ready) {  // else bev_ipm_warp_fuse_boxes_f32 wrote them (same geometry, pool and knobs)
+        const int maxpix = pool / (V2_SL * 16) - 4;  // the kernel's own pool test
+        hipLaunchKernelGGL((k_warp_boxes<TH>), dim3((unsigned)(((int64_t)ntiles * V + 255) / 256), B), dim3(256), 0,
+                           st, Hmat, xs, ys, V, Hf, Wf, sx, sy, Hb, Wb, maxpix, (Hb + TH - 1) / TH, boxes, spans,
+                           g_warp_span_pct);
+    }
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, block, lds, st, feats, sN, sH, sW, Hmat, xs, ys, B, V, C, Hf, Wf, sx, sy, Hb, Wb,
+                           out, pool, boxes, rpr, g_warp_tile_band > 0 ? g_warp_tile_band : (V >= 12 ? 4 : 1));
+    };
+    // one instantiation per mode (which fixes the occupancy, v2_occ), output layout and span staging on / off
+    auto layout = [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (nhwc)
+            spans ? go(k_warp_fuse_v2<M, TH, false, true, true>) : go(k_warp_fuse_v2<M, TH, false, true, false>);
+        else if (ck)
+            spans ? go(k_warp_fuse_v2<M, TH, true, false, true>) : go(k_warp_fuse_v2<M, TH, true, false, false>);
+        else
+            spans ? go(k_warp_fuse_v2<M, TH, false, false, true>) : go(k_warp_fuse_v2<M, TH, false, false, false>);
+    };
+    if (mode == BEV_FUSE_SUM) layout(std::integral_constant<int, BEV_FUSE_SUM>());
+    else if (mode == BEV_FUSE_MEAN) layout(std::integral_constant<int, BEV_FUSE_MEAN>());
+    else layout(std::integral_constant<int, BEV_FUSE_MAX>());
+    return last();
 }
 
 int warp_fuse_impl(const float *feats, int64_t sN, int64_t sC, int64_t sH, int64_t sW, const float *Hmat,
@@ -2406,10 +1963,6 @@ int warp_tune(int knob, int value) {
             slot = &g_warp_bwd_pool;
             ok = value >= 0 && value <= WARP_BWD_POOL_MAX;
             break;
-        case BEV_TUNE_WARP_PERSIST:
-            slot = &g_warp_persist;
-            ok = value >= 0 && value <= 2;
-            break;
         case BEV_TUNE_WARP_SPAN:
             slot = &g_warp_span_pct;
             ok = value >= 0 && value <= 100;
@@ -2430,7 +1983,7 @@ int warp_tune(int knob, int value) {
 
 extern "C" {
 
-int bev_abi_version(void) { return 13; }
+int bev_abi_version(void) { return 14; }
 
 #if WARP_STAMP
 int bev_warp_stamp_read(unsigned long long *host, int n) {  // timing builds only
@@ -2486,10 +2039,10 @@ int bev_ipm_warp_f32(const float *feats, int64_t sN, int64_t sC, int64_t sH, int
 int64_t bev_ipm_warp_fuse_workspace_bytes(int B, int V, int Hb, int Wb) {
     if (B < 0 || V <= 0 || Hb < 0 || Wb < 0) return BEV_ERR_ARGS;
     // per-(frame, tile, view) footprint boxes (16 x 16 tiles, v2 and v3; A/B builds of v2 with 8 x 32 tiles have as
-    // many), the work-queue words and the span tables
+    // many) and the span tables
     constexpr int TH = WARP_TILE_H, TW = FT_NT / TH;
     const int64_t nt = (((int64_t)Wb + TW - 1) / TW) * (((int64_t)Hb + TH - 1) / TH);
-    return BOX_HDR + (int64_t)B * nt * V * (int64_t)sizeof(uint2) + WQ_WORDS * (int64_t)sizeof(unsigned) +
+    return BOX_HDR + (int64_t)B * nt * V * (int64_t)sizeof(uint2) +
            (int64_t)B * nt * V * SPAN_ROWS * (int64_t)sizeof(unsigned);
 }
 
@@ -2545,12 +2098,10 @@ int bev_ipm_warp_fuse_boxes_f32(const float *Hmat, const float *xs, const float 
     constexpr int TH = WARP_TILE_H, TW = FT_NT / TH;
     const int ntiles = ((Wb + TW - 1) / TW) * ((Hb + TH - 1) / TH);
     const int maxpix = v2_pool_bytes(mode) / (V2_SL * 16) - 4;  // k_warp_fuse_v2's own pool test
-    unsigned *queue = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(workspace) + BOX_HDR +
-                                                   (int64_t)B * ntiles * V * (int64_t)sizeof(uint2));
+    uint2 *boxes = reinterpret_cast<uint2 *>(reinterpret_cast<unsigned char *>(workspace) + BOX_HDR);
     hipLaunchKernelGGL((k_warp_boxes<TH>), dim3((unsigned)(((int64_t)ntiles * V + 255) / 256), B), dim3(256), 0,
                        (hipStream_t)stream, Hmat, xs, ys, V, Hf, Wf, sx, sy, Hb, Wb, maxpix, (Hb + TH - 1) / TH,
-                       reinterpret_cast<uint2 *>(reinterpret_cast<unsigned char *>(workspace) + BOX_HDR), queue,
-                       span_tables(queue, g_warp_persist != 0), g_warp_span_pct);
+                       boxes, span_tables(boxes, (int64_t)B * ntiles * V), g_warp_span_pct);
     return last();
 }
 
