@@ -129,6 +129,22 @@ __device__ __forceinline__ float act_x(float t, int act) {
     return t;
 }
 
+// A run-time activation code as a compile-time one: dispatched once per kernel (wave-uniform), so the element
+// loops that apply it carry no scalar branch.
+template <int ACT>
+__device__ __forceinline__ float act_c(float t) {
+    if constexpr (ACT == 2) return silu_hw(t);
+    else if constexpr (ACT == 1) return t > 0.0f ? t : 0.0f;
+    else return t;
+}
+
+template <class F>
+__device__ __forceinline__ void act_dispatch(int act, F &&f) {
+    if (act == 2) f(std::integral_constant<int, 2>{});
+    else if (act == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
 // The wave's (TM*32) x (TN*32) accumulator tile goes through LDS, 32 rows per pass (4 * 32 * (TN * 32 + 4) floats
 // for the block), so every lane stores whole float4 row pieces; each pass issues all its residual loads at once (the
 // memory-bound 1x1 layers).  Same scheme as bev_conv.hip's epilogue.  With a.ys the result is stored split.
@@ -168,64 +184,67 @@ __device__ __forceinline__ void x6_epilogue(const ConvX &a, float *lds, const f3
             bv.w = n + 3 < a.Co ? a.bias[n + 3] : 0.f;
         }
     }
+    act_dispatch(a.act, [&](auto ac) {  // the activation is a compile-time constant of the element loops
+        constexpr int ACT = decltype(ac)::value;
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        // same-wave LDS operations complete in order: the previous pass's reads precede these writes
+        for (int i = 0; i < TM; ++i) {
+            // same-wave LDS operations complete in order: the previous pass's reads precede these writes
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+            for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) E[((r & 3) + 8 * (r >> 2) + 4 * h) * ER + j * 32 + r32] = acc[i][j][r];
-        const int64_t mbase = m0 + wm * TM * 32 + i * 32;
-        if (i > 0) res_load(i);
+                for (int r = 0; r < 16; ++r) E[((r & 3) + 8 * (r >> 2) + 4 * h) * ER + j * 32 + r32] = acc[i][j][r];
+            const int64_t mbase = m0 + wm * TM * 32 + i * 32;
+            if (i > 0) res_load(i);
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int row = rq + RPI * q;
-            const int64_t m = mbase + row;
-            if (m >= a.M) continue;
-            const float4 v = *(const float4 *)(E + row * ER + c4 * 4);
-            float o[4] = {v.x + bv.x, v.y + bv.y, v.z + bv.z, v.w + bv.w};
-            if (a.ys) {  // split output planes (the next conv's pre-split operand); ldy == Co, Co % 4 == 0
-                if (a.res) {
-                    const float4 rr = rv[q];
-                    o[0] += rr.x, o[1] += rr.y, o[2] += rr.z, o[3] += rr.w;
+            for (int q = 0; q < NQ; ++q) {
+                const int row = rq + RPI * q;
+                const int64_t m = mbase + row;
+                if (m >= a.M) continue;
+                const float4 v = *(const float4 *)(E + row * ER + c4 * 4);
+                float o[4] = {v.x + bv.x, v.y + bv.y, v.z + bv.z, v.w + bv.w};
+                if (a.ys) {  // split output planes (the next conv's pre-split operand); ldy == Co, Co % 4 == 0
+                    if (a.res) {
+                        const float4 rr = rv[q];
+                        o[0] += rr.x, o[1] += rr.y, o[2] += rr.z, o[3] += rr.w;
+                    }
+                    bf16x4 hv, mv, lv;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        __bf16 h_, m_, l_;
+                        split3(act_c<ACT>(o[u]), h_, m_, l_);
+                        hv[u] = h_, mv[u] = m_, lv[u] = l_;
+                    }
+                    __bf16 *yp = a.ys + m * a.Co + n;
+                    if (n < a.Co) {
+                        *(bf16x4 *)yp = hv;
+                        *(bf16x4 *)(yp + a.yps) = mv;
+                        *(bf16x4 *)(yp + 2 * a.yps) = lv;
+                    }
+                    continue;
                 }
-                bf16x4 hv, mv, lv;
+                float *yp = a.y + m * a.ldy + n;
+                if (nvec) {
+                    if (a.res) {
+                        o[0] += rv[q].x;
+                        o[1] += rv[q].y;
+                        o[2] += rv[q].z;
+                        o[3] += rv[q].w;
+                    }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    __bf16 h_, m_, l_;
-                    split3(act_x(o[u], a.act), h_, m_, l_);
-                    hv[u] = h_, mv[u] = m_, lv[u] = l_;
-                }
-                __bf16 *yp = a.ys + m * a.Co + n;
-                if (n < a.Co) {
-                    *(bf16x4 *)yp = hv;
-                    *(bf16x4 *)(yp + a.yps) = mv;
-                    *(bf16x4 *)(yp + 2 * a.yps) = lv;
-                }
-                continue;
-            }
-            float *yp = a.y + m * a.ldy + n;
-            if (nvec) {
-                if (a.res) {
-                    o[0] += rv[q].x;
-                    o[1] += rv[q].y;
-                    o[2] += rv[q].z;
-                    o[3] += rv[q].w;
-                }
+                    for (int u = 0; u < 4; ++u) o[u] = act_c<ACT>(o[u]);
+                    *(float4 *)yp = make_float4(o[0], o[1], o[2], o[3]);
+                } else {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) o[u] = act_x(o[u], a.act);
-                *(float4 *)yp = make_float4(o[0], o[1], o[2], o[3]);
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (n + u >= a.Co) break;
-                    float t = o[u];
-                    if (a.res) t += a.res[m * a.Co + n + u];
-                    yp[u] = act_x(t, a.act);
+                    for (int u = 0; u < 4; ++u) {
+                        if (n + u >= a.Co) break;
+                        float t = o[u];
+                        if (a.res) t += a.res[m * a.Co + n + u];
+                        yp[u] = act_c<ACT>(t);
+                    }
                 }
             }
         }
-    }
+    });
 }
 
 template <int WM, int WN, int TM, int TN, bool DUAL>
@@ -420,66 +439,141 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
 // Chained bottleneck body in the split arithmetic (bev_conv2d_chain_x6_f32): timm Bottleneck without a downsample,
 // act3(bn3(conv3(act2(bn2(conv2(h1))))) + x).  The block's BM x BN tile of h2 = act(conv2 + b2) holds EVERY channel
 // of h2 for its BM pixels (BN == Co), so it is split once into three bf16 planes in LDS ([3][BM][BN + 8]: rows of
-// odd 16-B slot counts) and conv3 (1x1, K2 = BN) runs on it there: h2 never makes its HBM round trip.  Wave w takes
-// rows 32 w .. 32 w + 31 and walks Co2 in 64-column chunks (2 MFMA tiles); the W3 fragments come from the
-// fragment-order panel by buffer loads (SGPR soffset); the chunk's residual is loaded before its MFMAs; residual and
-// output are addressed by buffer instructions (row in the VGPR offset, so rows past M read 0 / are dropped).
+// odd 16-B slot counts) and conv3 (1x1, K2 = BN) runs on it there: h2 never makes its HBM round trip.  Each wave
+// takes a 32-row band and walks Co2 in 32-column blocks; the W3 fragments reach it through LDS (LDS-DMA from the
+// fragment-order panel, one step ahead); a block's residual is loaded one block ahead; residual and output are
+// addressed by buffer instructions (row in the VGPR offset, so rows past M read 0 / are dropped).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t x6_rsrc(const void *p, int64_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)(uint32_t)bytes, 0x00020000);
 }
 
+__device__ __forceinline__ unsigned lds_addr(const void *p) {
+    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
+}
+
+__device__ __forceinline__ void dma16(const void *src, unsigned dst_any) {
+    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)dst_any);  // wave-uniform LDS address
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(src), "s"(dst)
+        : "memory");
+}
+
+// this wave's older vector-memory operations have completed except the newest N (vmcnt retires in issue order), its
+// LDS reads have returned, and every wave of the workgroup has got here
+template <int N>
+__device__ __forceinline__ void x6_wait_barrier() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+
+// LDS of a chain kernel's epilogue: the three h2 planes, then one W3 stage (the second stage overlays the planes
+// once every wave holds its h2 fragments in registers): WPB column blocks x 4 slices x 3 planes of 1 KiB
+template <int BM, int BN>
+__host__ __device__ constexpr int x6_chain_lds_bytes() { return 3 * BM * (BN + 8) * 2 + (4 / (BM / 32)) * 12288; }
+
+// The chain epilogue.  h2 = act(conv2 + b2) is split into the three LDS planes; every wave then takes the h2
+// fragments of its 32-row band (all S2 slices, three planes) into registers ONCE and walks Co2 in 32-column blocks:
+// wave = (band, part), part = which of the WPB column blocks of a step (WPB = 2 for the 64-row tile, so the four
+// waves of a workgroup always work on the same W3 stage and the panel is read once per tile).  The W3 panel (the
+// dual's [W3 | Wds]) reaches the MFMAs through LDS: a step = 4 slices x WPB column blocks = 12 WPB fragment runs
+// of 1 KiB, copied by LDS-DMA one step ahead into one of two stages and read back as ds_read_b128, so no MFMA waits
+// on a vector-memory load of its own.  The stages: [HB, HB + 12 WPB KiB) after the planes, and [0, 12 WPB KiB) over
+// the planes, which are dead once the fragments are in registers (the barrier of step 0 orders the two).
+// Issue order per step s (the vmcnt waits below count on it; vmcnt retires in issue order):
+//     wait for this wave's DMAs of step s, barrier | DMAs of step s + 1 | first step of a block: bias2 + residual
+//     of the NEXT block | 24 MFMAs | last step of a block: the block's 16 stores.
+// The wait in front of step s therefore leaves in flight exactly what was issued after the DMAs of step s: the
+// previous block's stores and the look-ahead residual are never drained in front of an MFMA, and a residual load
+// has two steps of MFMAs to arrive.  The residual sits in two register sets used alternately (no copies).
 // X2S > 0: the dual form (block 0 of a stage, bev_conv2d_chain_dual_x6_f32): conv3's K continues with the X2S
 // 16-deep slices of the shortcut operand x2 at the lane row's strided pixel (the 1x1 downsample), split in registers
-// once per wave and reused by every chunk; the panel is the dual tail's [W3 | Wds].
+// once per wave and reused by every block; the panel is the dual tail's [W3 | Wds].
+// Per output element: slices ascending, the six products of a slice in the mainloop's order, (acc + bias2) +
+// residual, then act2 -- the separate launches' arithmetic.
 template <int WM, int WN, int TM, int TN, int X2S = 0>
 __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char *lds_raw, const f32x16 (&acc)[TM][TN],
                                                   int wave, int lane, int wm, int wn, int64_t m0) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32, HR = BN + 8, HPL = BM * HR;
-    constexpr int NB = BM / 32, WPB = 4 / NB;  // 32-row bands; waves per band (each a share of the Co2 chunks)
+    constexpr int NB = BM / 32, WPB = 4 / NB;  // 32-row bands; waves per band (each one column block of a step)
     static_assert(NB * WPB == 4, "chain epilogue: 4 waves over the 32-row bands");
+    constexpr int S2 = BN / 16;   // 16-deep slices of conv3's K from h2
+    constexpr int ST = S2 + X2S;  // slices of the panel
+    constexpr int U = ST / 4;     // steps (4 slices) per column block
+    static_assert(ST % 4 == 0, "chain epilogue: whole 4-slice steps");
+    constexpr int HB = 3 * HPL * 2;  // bytes of the h2 planes = offset of W3 stage 0
+    constexpr int PW = WPB * 3;      // 1-KiB DMA pieces per wave and step
+    static_assert(HB % 1024 == 0, "W3 stage 0 starts on a fragment boundary");
     __bf16 *H = (__bf16 *)lds_raw;
     const int r32 = lane & 31, hh = lane >> 5;
-    // residual of this wave's first chunk: requested before the h2 staging, so its latency overlaps it
     const int band = (wave % NB) * 32, part = wave / NB;
     const int64_t rows = (a.M - m0 < BM) ? a.M - m0 : BM;
     const int64_t base = m0 * a.Co2;
-    const __amdgpu_buffer_rsrc_t rr = x6_rsrc(a.res ? a.res + base : a.y + base, rows * a.Co2 * 4);
+    const float *resp = a.res ? a.res + base : a.y + base;
+    const float *biasp = a.bias2 ? a.bias2 : a.y;
+    const int64_t resb = rows * a.Co2 * 4, biasb = a.bias2 ? (int64_t)a.Co2 * 4 : 0;  // no bias2: an empty buffer (0)
     const int vo = ((band + 4 * hh) * a.Co2 + r32) * 4;  // lane part of a res / y address
-    const int nch = a.Co2 / 64 / WPB;                     // this wave's 64-column chunks: [part * nch, (part + 1) * nch)
-    float rvn[2][16];
-    auto res_load = [&](int c0) {
-        if (!a.res) return;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
+    const int NG = a.Co2 / (32 * WPB);                    // column blocks of this wave: 32 (g WPB + part), g < NG
+    // bias2 ([16]) and residual ([0..15], HR) of the wave's block at column c0.  !live (the look-ahead of the last
+    // block): the same instructions on empty buffers -- no memory access, and the loop's vmcnt counts hold as they are
+    auto res_load = [&](auto hr, int c0, float(&rv)[17], bool live) {
+        const __amdgpu_buffer_rsrc_t rr = x6_rsrc(resp, live ? resb : 0), rb = x6_rsrc(biasp, live ? biasb : 0);
+        rv[16] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, r32 * 4, c0 * 4, 0));
+        if constexpr (decltype(hr)::value) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                rvn[j][r] = __builtin_bit_cast(
-                    float, __builtin_amdgcn_raw_buffer_load_b32(rr, vo + ((r & 3) + 8 * (r >> 2)) * a.Co2 * 4,
-                                                                (c0 + 32 * j) * 4, 0));
-    };
-    res_load(64 * part * nch);
-    __syncthreads();  // every wave is done with the staging buffers
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int col = wn * TN * 32 + j * 32 + r32;
-            const float bj = a.bias ? a.bias[col] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                __bf16 h_, m_, l_;
-                split3(act_x(acc[i][j][r] + bj, a.act), h_, m_, l_);
-                const int row = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                H[row * HR + col] = h_;
-                H[HPL + row * HR + col] = m_;
-                H[2 * HPL + row * HR + col] = l_;
-            }
+                rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                                      rr, vo + ((r & 3) + 8 * (r >> 2)) * a.Co2 * 4, c0 * 4, 0));
         }
+    };
+    const unsigned lbase = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr(lds_raw));
+    const __bf16 *wsrc = a.wp2 + lane * 8;
+    // this wave's share of step (g, u)'s fragment runs -> the stage at byte sbo: piece q = (column block of the
+    // step, slice of the step, plane) is panel run ((g WPB + cbl) ST + 4 u) 3 + q % 12
+    auto issue_w3 = [&](int g, int u, unsigned sbo) {
+#pragma unroll
+        for (int i = 0; i < PW; ++i) {
+            const int q = wave + 4 * i, cbl = q / 12, r = q % 12;
+            dma16(wsrc + (((int64_t)(g * WPB + cbl) * ST + 4 * u) * 3 + r) * 512, lbase + sbo + (unsigned)(q * 1024));
+        }
+    };
+    // first block's residual: requested before the h2 staging, so its latency overlaps it
+    float rv[2][17];
+    if (a.res) res_load(std::true_type{}, 32 * part, rv[0], true);
+    else res_load(std::false_type{}, 32 * part, rv[0], true);
+    __syncthreads();  // every wave is done with the staging buffers
+    issue_w3(0, 0, HB);
+    act_dispatch(a.act, [&](auto ac) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = wn * TN * 32 + j * 32 + r32;
+                const float bj = a.bias ? a.bias[col] : 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    __bf16 h_, m_, l_;
+                    split3(act_c<decltype(ac)::value>(acc[i][j][r] + bj), h_, m_, l_);
+                    const int row = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                    H[row * HR + col] = h_;
+                    H[HPL + row * HR + col] = m_;
+                    H[2 * HPL + row * HR + col] = l_;
+                }
+            }
+    });
     __syncthreads();
-    constexpr int S2 = BN / 16;      // 16-deep slices of conv3's K from h2
-    constexpr int ST = S2 + X2S;     // slices of the panel
-    bf16x8 fx[X2S > 0 ? X2S : 1][3];  // the shortcut operand, split (dual form)
+    bf16x8 fa[ST][3];  // conv3's A fragments of the band: h2, then the split shortcut operand (dual form)
+    {
+        const __bf16 *ap = H + (band + r32) * HR + 8 * hh;
+#pragma unroll
+        for (int t = 0; t < S2; ++t)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) fa[t][p] = *(const bf16x8 *)(ap + p * HPL + 16 * t);
+    }
     if constexpr (X2S > 0) {
         int64_t m = m0 + band + r32;
         const bool ok = m < a.M;
@@ -497,61 +591,76 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
             for (int e = 0; e < 8; ++e) {
                 __bf16 h_, m_, l_;
                 split3(e < 4 ? v0[e] : v1[e - 4], h_, m_, l_);
-                fx[t][0][e] = h_, fx[t][1][e] = m_, fx[t][2][e] = l_;
+                fa[S2 + t][0][e] = h_, fa[S2 + t][1][e] = m_, fa[S2 + t][2][e] = l_;
             }
         }
     }
-    const __bf16 *ap = H + (band + r32) * HR + 8 * hh;
+    // everything this wave has issued so far is complete: the counted waits of the loop start from an empty queue
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     const __amdgpu_buffer_rsrc_t ry = x6_rsrc(a.y + base, rows * a.Co2 * 4);
-    const __amdgpu_buffer_rsrc_t rw = x6_rsrc(a.wp2, copad_x(a.Co2) / 32 * (int64_t)ST * 3072);
-    const int vl = lane * 16;
-    for (int nc = part * nch; nc < (part + 1) * nch; ++nc) {
-        const int c0 = 64 * nc;
-        float rv[2][16];
+    // one column block: rc = its bias2 / residual (loaded during the previous block), rn = the next block's
+    auto block = [&](auto hr, auto a2, int g, float(&rc)[17], float(&rn)[17]) {
+        constexpr bool HAS_RES = decltype(hr)::value;
+        constexpr int R = HAS_RES ? 17 : 1;  // loads of one res_load
+        const bool more = g + 1 < NG;
+        const int c0 = 32 * (g * WPB + part);
+        f32x16 acc2 = (f32x16){0};
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) rv[j][r] = rvn[j][r];
-        if (nc + 1 < (part + 1) * nch) res_load(c0 + 64);  // the next chunk's residual, during these MFMAs
-        f32x16 acc2[2] = {(f32x16){0}, (f32x16){0}};
-#pragma unroll
-        for (int t = 0; t < ST; ++t) {
-            bf16x8 fa[3], fb[2][3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                if constexpr (X2S > 0) fa[p] = t < S2 ? *(const bf16x8 *)(ap + p * HPL + 16 * (t < S2 ? t : 0))
-                                                      : fx[t >= S2 ? t - S2 : 0][p];
-                else fa[p] = *(const bf16x8 *)(ap + p * HPL + 16 * t);
+        for (int u = 0; u < U; ++u) {
+            // in flight behind this step's DMAs (issued one step ago): see the issue order above
+            if constexpr (U == 1) x6_wait_barrier<R + 16>();
+            else if (u == 0) x6_wait_barrier<16>();
+            else if (u == 1) x6_wait_barrier<R>();
+            else x6_wait_barrier<0>();
+            const unsigned sbo = ((g * U + u) & 1) ? 0u : (unsigned)HB;
+            if (u + 1 < U) issue_w3(g, u + 1, (unsigned)HB - sbo);
+            else if (more) issue_w3(g + 1, 0, (unsigned)HB - sbo);
+            if (u == 0) {
+                res_load(hr, c0 + 32 * WPB, rn, more);
+                asm volatile("" ::: "memory");  // the loads stay here, in front of the step's LDS reads and MFMAs
             }
+            const __bf16 *Bs = (const __bf16 *)(lds_raw + sbo) + part * (12 * 512) + lane * 8;
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int sl = 0; sl < 4; ++sl) {
+                const int t = 4 * u + sl;
+                bf16x8 fb[3];
 #pragma unroll
-                for (int p = 0; p < 3; ++p)
-                    fb[j][p] = __builtin_bit_cast(
-                        bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, vl, (((c0 >> 5) + j) * ST + t) * 3072 + p * 1024, 0));
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][0], acc2[j], 0, 0, 0);
-                acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][1], acc2[j], 0, 0, 0);
-                acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[j][0], acc2[j], 0, 0, 0);
-                acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][2], acc2[j], 0, 0, 0);
-                acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[j][0], acc2[j], 0, 0, 0);
-                acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[j][1], acc2[j], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float bj = a.bias2 ? a.bias2[c0 + 32 * j + r32] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float o = acc2[j][r] + bj;
-                if (a.res) o += rv[j][r];
-                o = act_x(o, a.act2);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), ry,
-                                                      vo + ((r & 3) + 8 * (r >> 2)) * a.Co2 * 4, (c0 + 32 * j) * 4, 0);
+                for (int p = 0; p < 3; ++p) fb[p] = *(const bf16x8 *)(Bs + (sl * 3 + p) * 512);
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][0], fb[0], acc2, 0, 0, 0);
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][0], fb[1], acc2, 0, 0, 0);
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][1], fb[0], acc2, 0, 0, 0);
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][0], fb[2], acc2, 0, 0, 0);
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][2], fb[0], acc2, 0, 0, 0);
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][1], fb[1], acc2, 0, 0, 0);
             }
         }
-    }
+        const float bj = rc[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float o = acc2[r] + bj;
+            if constexpr (HAS_RES) o += rc[r];
+            o = act_c<decltype(a2)::value>(o);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), ry,
+                                                  vo + ((r & 3) + 8 * (r >> 2)) * a.Co2 * 4, c0 * 4, 0);
+        }
+    };
+    auto run = [&](auto hr, auto a2) {
+        // the first block's residual has arrived (the wait above); using it here tells the compiler so, and its own
+        // waits inside the loop count from the loop's loads alone
+        asm volatile("" ::"v"(rv[0][16]));
+        if constexpr (decltype(hr)::value) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(rv[0][r]));
+        }
+        for (int g = 0; g < NG; g += 2) {
+            block(hr, a2, g, rv[0], rv[1]);
+            if (g + 1 < NG) block(hr, a2, g + 1, rv[1], rv[0]);
+        }
+    };
+    act_dispatch(a.act2, [&](auto a2) {
+        if (a.res) run(std::true_type{}, a2);
+        else run(std::false_type{}, a2);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -796,7 +905,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
     constexpr int APL = BM * YROW;                 // bf16 per A plane
     constexpr int STAGE = 3 * APL;                 // bf16 per LDS stage
     constexpr int AQ = BM / 32;                    // A float4 per thread and K step: rows tid / 8 + 32 q
-    constexpr int EPIB = CHAIN ? 3 * BM * (BN + 8) * 2 : x6_epi_bytes<TN>();
+    constexpr int EPIB = CHAIN ? x6_chain_lds_bytes<BM, BN>() : x6_epi_bytes<TN>();
     constexpr int LDSB = (2 * STAGE * 2 > EPIB) ? 2 * STAGE * 2 : EPIB;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDSB];
     __bf16 *lds = (__bf16 *)lds_raw;
@@ -1006,21 +1115,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
 // the SGPR soffset (no address VALU).  NHWC, Ci % 32 == 0.  Same per-output K order as k_conv_x6 / k_conv_x6b:
 // bit-identical results on the same split operands.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned lds_addr(const void *p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-
-__device__ __forceinline__ void dma16(const void *src, unsigned dst_any) {
-    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)dst_any);  // wave-uniform LDS address
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(dst)
-        : "memory");
-}
-
 // CHAIN (bev_conv2d_chain_x6_f32 / _dual_ with a pre-split xs): the mainloop above, then x6_chain_epilogue exactly
 // as k_conv_x6b's chain runs it -- the layer1 / layer2 bottleneck bodies take conv1's split output, so conv2 (the
 // 3x3, whose fp32 operand the register-staged kernel splits once per tap) stages by DMA alone.
@@ -1037,7 +1131,7 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
     constexpr int RW = BM / 4;       // rows staged by each wave
     constexpr int RG = RW / 16;      // 16-row DMA groups per wave and plane
     constexpr int BPW = BLDS ? BN / 32 * 6 / 4 : 0;  // B pieces (1 KiB) per wave and K step
-    constexpr int EPIB = CHAIN ? 3 * BM * (BN + 8) * 2 : x6_epi_bytes<TN>();
+    constexpr int EPIB = CHAIN ? x6_chain_lds_bytes<BM, BN>() : x6_epi_bytes<TN>();
     constexpr int LDSB = (2 * STAGE * 2 > EPIB) ? 2 * STAGE * 2 : EPIB;
     static_assert(RW % 16 == 0, "whole DMA groups per wave");
     static_assert(!BLDS || (BN / 32 * 6) % 4 == 0, "whole B pieces per wave");
