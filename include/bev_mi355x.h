@@ -33,7 +33,7 @@ extern "C" {
 #define BEV_FUSE_MEAN 1
 #define BEV_FUSE_MAX 2
 
-/* ABI version (bumped on any signature change): 14. */
+/* ABI version (bumped on any signature change): 15. */
 int bev_abi_version(void);
 
 /* host: provenance -- the first 16 hex digits of sha256 over the library's HIP sources and headers (the
@@ -67,6 +67,9 @@ const char *bev_build_source_hash(void);
  *   0 (64-column tiles for Co <= 64), and the 64-pixel-step weight gradient; 1 = the 32-deep-step conv and
  *   32-pixel-step weight gradient always; 2 = as 0 with 128-column tiles always.  Same conv results bit for bit;
  *   weight gradients equal to fp32 tolerance (pixel chunks differ).
+ * BEV_TUNE_CONV_H16_BUF: fp16-stored operands of the fp16 convs: 1 (default) = staged by raw buffer loads with 32-bit
+ *   offsets where the operand and the panel are below 2 GiB, 0 = by 64-bit pointers always (the form larger operands
+ *   take).  Same results bit for bit.
  * BEV_TUNE_CONV_PW_SMALL: narrow / tiny-K 1x1 convs (EfficientNet): 0 = the MFMA tiles; 1 = Co in
  *   {16, 24, 32, 40, 48} on a per-pixel VALU kernel (measured slower, kept for A/B); 2 (default) = 1x1 with
  *   Ci in {24, 32, 40, 48} and Co <= 32 on a wave-streaming MFMA kernel (k_pw_mfma, float4 epilogue through
@@ -109,6 +112,7 @@ const char *bev_build_source_hash(void);
 /* 18 (a persistent work-queue fused warp, removed with ABI 14) is not reused */
 #define BEV_TUNE_WARP_SPAN 19
 #define BEV_TUNE_WARP_TILE_BAND 20
+#define BEV_TUNE_CONV_H16_BUF 21
 int bev_tune(int knob, int value);
 
 /* ---------------------------------------------------------------------------
@@ -518,6 +522,22 @@ int bev_conv2d_h16_h16(const void *x, int x_half, int N, int H, int W, int Ci, c
                        const float *bias, const uint16_t *residual, int Co, int KH, int KW, int stride, int pad,
                        int dilation, int act, uint16_t *y, int Ho, int Wo, void *stream);
 
+/* The "f16" arithmetic of the BEV head in inference (the reference validates in eval() under autocast(float16),
+ * train.py:285-286, which puts the convs of detector.py:16-30 on fp16): bev_conv2d_h16_h16's convolution with the
+ * previous layer's GroupNorm affine + ReLU applied to the fp16-stored operand while it is staged,
+ *     x'[n][p][ci] = f16_rne( relu?( float(x[n][p][ci]) * in_scale[n][ci] + in_shift[n][ci] ) )   (one fp32 multiply,
+ * then one fp32 add: bev_groupnorm_apply_ex_f32's expression and rounding) for in-range taps -- zero padding stays 0
+ * -- so the normalised map is never written.  in_scale / in_shift [N][Ci] fp32, 16-B aligned (both NULL: plain conv;
+ * non-NULL needs x_half = 1); x NHWC fp32 (x_half = 0: rounded while staging) or fp16; packed the
+ * bev_conv_pack_weights_h16 panel; fp32 accumulation, bias (may be NULL) and act 0 / 1 / 2 as there.  y_half = 1: y
+ * dense NHWC fp16 [N][Ho][Wo][Co], rounded once after bias and act, Co % 8 == 0, ldy == Co, 16-B aligned; y_half = 0:
+ * y fp32 with rows ldy >= Co floats apart, not rounded.  Ci % 64 == 0, x / packed 16-B aligned; anything else returns
+ * BEV_ERR_ARGS before any launch.  N == 0 is a no-op. */
+int bev_conv2d_h16_affine(const void *x, int x_half, int N, int H, int W, int Ci, const float *in_scale,
+                          const float *in_shift, int in_relu, const uint16_t *packed, const float *bias, int Co, int KH,
+                          int KW, int stride, int pad, int dilation, int act, void *y, int y_half, int ldy, int Ho,
+                          int Wo, void *stream);
+
 /* Weight gradient of a convolution under autocast(float16): dW[co][(ky*KW + kx)*Ci + ci] =
  * sum over output pixels of f16(dz) * f16(x) with fp32 accumulation (the fp16 matrix cores), dW [Co][KH*KW*Ci]
  * fp32 (zeroed by the call).  x [N,H,W,Ci], dz [N,Ho,Wo,Co] NHWC fp32, Ci % 4 == 0, Co % 4 == 0, 16-B aligned.
@@ -647,6 +667,13 @@ int64_t bev_groupnorm_workspace_bytes(int N, int64_t P, int C, int G);
 int bev_groupnorm_fwd_f32(const float *x, int N, int64_t P, int C, int G, float eps, const float *gamma,
                           const float *beta, float *mean, float *rstd, float *scale, float *shift, void *workspace,
                           void *stream);
+
+/* bev_groupnorm_fwd_f32 with x stored in fp32 (x_half = 0) or fp16 (x_half = 1; 8-B aligned): the statistics of the
+ * stored values, summed in double in the same thread map, pixel blocks and order -- bitwise the fp32 call's results
+ * on the upcast map. */
+int bev_groupnorm_fwd_ex_f32(const void *x, int x_half, int N, int64_t P, int C, int G, float eps, const float *gamma,
+                             const float *beta, float *mean, float *rstd, float *scale, float *shift, void *workspace,
+                             void *stream);
 
 /* device: y = x * scale + shift (+ ReLU), NHWC [N][P][C]; y may alias x. */
 int bev_groupnorm_apply_f32(const float *x, int N, int64_t P, int C, const float *scale, const float *shift, int relu,

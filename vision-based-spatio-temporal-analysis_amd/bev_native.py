@@ -20,7 +20,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libbev_mi355x.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 BEV_ERR_ARGS = -1  # include/bev_mi355x.h: an argument the kernel cannot take
 
 FUSE_MODES = {"sum": 0, "mean": 1, "max": 2}
@@ -137,6 +137,9 @@ SIGNATURES = {
                                    _vp, _vp]),
     "bev_conv_wgrad_h16_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "bev_conv2d_h16_h16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "bev_conv2d_h16_affine": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i,
+                                   _i, _i, _i, _vp]),
+    "bev_groupnorm_fwd_ex_f32": (_i, [_vp, _i, _i, _i64, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bev_batchnorm_apply_ex_f32": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "bev_batchnorm_bwd_ex_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp,
                                       _vp, _vp]),
@@ -265,6 +268,7 @@ TUNE_CONV_X6_NT = 16
 TUNE_STEM3_STAGE = 17
 TUNE_WARP_SPAN = 19
 TUNE_WARP_TILE_BAND = 20
+TUNE_CONV_H16_BUF = 21
 WARP_KERNEL_DMA, WARP_KERNEL_REGISTER = 0, 1
 
 
@@ -339,6 +343,38 @@ def conv_arith_mode(mode: str):
         yield
     finally:
         set_conv_arith(prev)
+
+
+# Arithmetic of the BEV detection head (models/heads/detector.py) in inference, a switch of its own -- the trunk's
+# conv_arith_mode("f16") does not touch the head.  "f32" (default) = the exact-f32 MFMA convs with the GroupNorm
+# affine in their operand loader; "f16" (opt-in) = what the reference's validation forward computes for the head in
+# eval() under autocast(float16) (train.py:285-286): fp16 operands and weights on the fp16 matrix cores, fp32
+# accumulation, each stem conv's output rounded once to fp16 and kept in fp16, GroupNorm statistics (double sums) of
+# those stored values, the affine + ReLU applied in fp32 by the next conv's operand loader and rounded to fp16
+# (bev_conv2d_h16_affine), the 5-channel output fp32.  Training is not affected.
+HEAD_ARITHS = ("f32", "f16")
+_HEAD_ARITH = {"mode": "f32"}
+
+
+def head_arith() -> str:
+    return _HEAD_ARITH["mode"]
+
+
+def set_head_arith(mode: str) -> str:
+    """Select the inference arithmetic of the BEV head (HEAD_ARITHS); returns the previous mode."""
+    if mode not in HEAD_ARITHS:
+        raise ValueError(f"head arithmetic {mode!r} not in {HEAD_ARITHS}")
+    prev, _HEAD_ARITH["mode"] = _HEAD_ARITH["mode"], mode
+    return prev
+
+
+@contextlib.contextmanager
+def head_arith_mode(mode: str):
+    prev = set_head_arith(mode)
+    try:
+        yield
+    finally:
+        set_head_arith(prev)
 
 
 def half_convs() -> bool:
@@ -987,6 +1023,46 @@ def conv2d_h16_half(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, C
                                       _ptr(residual), Co, KH, KW, stride, pad, dilation, int(act), _ptr(y), Ho, Wo,
                                       _stream(x))
     _check(rc, "bev_conv2d_h16_h16")
+    return y
+
+
+def conv2d_h16_affine(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, K: int, pad: int, dilation: int = 1,
+                      in_scale: torch.Tensor = None, in_shift: torch.Tensor = None, in_relu: bool = False,
+                      y_half: bool = True, out: torch.Tensor = None, act: int = 0) -> torch.Tensor:
+    """The "f16" head conv (bev_conv2d_h16_affine): stride-1 KxK conv of x [N,H,W,Ci] NHWC (Ci % 64 == 0) stored in
+    fp16, or in fp32 without an affine, with the fp16 panel of pack_conv_weight_h16; in_scale / in_shift [N,Ci] fp32
+    (both or neither): the previous layer's GroupNorm affine (+ ReLU) applied to the fp16 operand while it is staged
+    and rounded to fp16 -- groupnorm_apply_half's values, never written.  y_half: y fp16 [N,Ho,Wo,Co] (Co % 8 == 0),
+    rounded once after bias and act; else fp32, and `out` may be a wider fp32 NHWC buffer [N,Ho,Wo,>=Co] whose first
+    Co channels receive y."""
+    x = x.contiguous()
+    _require_gpu_h(x)
+    _require_gpu(bias, in_scale, in_shift)
+    if not packed.is_cuda or packed.dtype != torch.float16:
+        raise HipError("conv2d_h16_affine needs the fp16 weight panel on the device")
+    if (in_scale is None) != (in_shift is None):
+        raise HipError("conv2d_h16_affine: in_scale and in_shift come together")
+    N, H, W, Ci = x.shape
+    if in_scale is not None:
+        if x.dtype != torch.float16:
+            raise HipError("conv2d_h16_affine: the operand affine needs an fp16-stored operand")
+        if tuple(in_scale.shape) != (N, Ci) or tuple(in_shift.shape) != (N, Ci):
+            raise HipError("conv2d_h16_affine: in_scale / in_shift are [N, Ci]")
+        in_scale, in_shift = in_scale.contiguous(), in_shift.contiguous()
+    Ho, Wo = H + 2 * pad - dilation * (K - 1), W + 2 * pad - dilation * (K - 1)
+    if out is not None:
+        want = torch.float16 if y_half else torch.float32
+        if not (out.is_cuda and out.dtype == want and tuple(out.shape[:3]) == (N, Ho, Wo) and out.is_contiguous()
+                and (out.shape[3] == Co if y_half else out.shape[3] >= Co)):
+            raise HipError("conv2d_h16_affine: out is a contiguous NHWC device tensor of the output's shape and type")
+        y = out
+    else:
+        y = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float16 if y_half else torch.float32)
+    with _span("conv", x):
+        rc = lib().bev_conv2d_h16_affine(_ptr(x), int(x.dtype == torch.float16), N, H, W, Ci, _ptr(in_scale),
+                                         _ptr(in_shift), int(in_relu), _ptr(packed), _ptr(bias), Co, K, K, 1, pad,
+                                         dilation, int(act), _ptr(y), int(y_half), y.shape[3], Ho, Wo, _stream(x))
+    _check(rc, "bev_conv2d_h16_affine")
     return y
 
 
@@ -1748,8 +1824,10 @@ def _gn_workspace(N, P, C, G, device):
 
 
 def groupnorm_fwd(x: torch.Tensor, G: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float):
-    """x [N,H,W,C] NHWC -> (mean [N,G], rstd [N,G], scale [N,C], shift [N,C])."""
-    _require_gpu(x, gamma, beta)
+    """x [N,H,W,C] NHWC, stored in fp32 or fp16 (the statistics of the stored values, bitwise those of the upcast
+    map) -> (mean [N,G], rstd [N,G], scale [N,C], shift [N,C]), fp32."""
+    _require_gpu_h(x)
+    _require_gpu(gamma, beta)
     assert x.is_contiguous()
     N, C = x.shape[0], x.shape[-1]
     P = x.numel() // (N * C)
@@ -1760,10 +1838,10 @@ def groupnorm_fwd(x: torch.Tensor, G: int, gamma: torch.Tensor, beta: torch.Tens
     shift = torch.empty(N, C, device=dev)
     ws = _gn_workspace(N, P, C, G, dev)
     with _span("groupnorm", x):
-        rc = lib().bev_groupnorm_fwd_f32(_ptr(x), N, P, C, G, float(eps), _ptr(gamma.detach().contiguous()),
-                                         _ptr(beta.detach().contiguous()), _ptr(mean), _ptr(rstd), _ptr(scale),
-                                         _ptr(shift), _ptr(ws), _stream(x))
-    _check(rc, "bev_groupnorm_fwd_f32")
+        rc = lib().bev_groupnorm_fwd_ex_f32(_ptr(x), int(x.dtype == torch.float16), N, P, C, G, float(eps),
+                                            _ptr(gamma.detach().contiguous()), _ptr(beta.detach().contiguous()),
+                                            _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(shift), _ptr(ws), _stream(x))
+    _check(rc, "bev_groupnorm_fwd_ex_f32")
     return mean, rstd, scale, shift
 
 

@@ -1534,6 +1534,7 @@ int bev_tune(int knob, int value) {
     if (knob == BEV_TUNE_CONV_X6_TILE || knob == BEV_TUNE_CONV_X6_KERNEL || knob == BEV_TUNE_CONV_X6_NT)
         return bev::conv_x6_tune(knob, value);
     if (knob == BEV_TUNE_CONV_H16_KERNEL) return bev::conv_h16_tune(value);
+    if (knob == BEV_TUNE_CONV_H16_BUF) return bev::conv_h16_buf_tune(value);
     if (knob == BEV_TUNE_DW_RUN) return bev::dw_tune(value);
     if (knob == BEV_TUNE_STEM3_STAGE) return bev::stem3_tune(value);
     if (knob == BEV_TUNE_CONV_PW_SMALL) {

@@ -33,6 +33,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // native vector: s
 constexpr int HBM = 128, HBN = 128, HBK = 32;
 int g_h16_kernel = 0;  // BEV_TUNE_CONV_H16_KERNEL: 0 = k_conv_h16b where Ci % 64 == 0 and k_wgrad_h16b, 1 = k_conv_h16
                        // and k_wgrad_h16 always
+int g_h16_buf = 1;     // BEV_TUNE_CONV_H16_BUF: 1 = fp16-stored operands staged by raw buffer loads where they apply,
+                       // 0 = the pointer form always (what operands of 2 GiB and more run on)
 constexpr int HROW = 40;  // halves per LDS row: 32 + 8 pad = 80 B = 5 slots (odd: 16 rows -> 16 distinct slots)
 
 __device__ __attribute__((aligned(16))) float g_hzero4[4] = {0.f, 0.f, 0.f, 0.f};  // never written
@@ -66,6 +68,9 @@ struct ConvH {
     float *__restrict__ stats;  // k_conv_h16b: per (row tile, channel) BatchNorm partials (sum, M2) of the output, or null
     int N, H, W, Ci, Co, KH, KW, stride, pad, dil, Ho, Wo, act, ldy, Kp;
     int64_t M;
+    const float *__restrict__ in_scale;  // k_conv_h16b<.., AFF = true>: the operand affine [N][Ci] (bev_conv2d_h16_affine)
+    const float *__restrict__ in_shift;
+    int in_relu;
 };
 
 __device__ __forceinline__ float act_h(float t, int act) {
@@ -311,8 +316,22 @@ __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&ac
 // of 2 B per lane at a pixel stride.  Same mainloop, same (acc + bias) + residual order as the fp32 epilogue: every
 // output is the fp32-output kernel's value rounded to fp16.  A template parameter, not a runtime branch: the
 // HOUT = false instances are unchanged.
-template <bool HIN, int BN, bool BUF = false, bool HOUT = false>
+// AFF (bev_conv2d_h16_affine; fp16 operand, whole-line map): the operand is the previous layer's conv output z stored
+// in fp16, and its GroupNorm affine + ReLU is applied between the staging registers and the LDS store,
+//     a = f16_rne( max( float(z) * scale[n][ci] + shift[n][ci], 0 ) )      (one fp32 multiply, one fp32 add)
+// -- k_gn_apply<_Float16>'s expression, so the LDS image is what that kernel would have written and the normalised
+// map never exists in HBM.  Only pieces whose tap is inside the image and whose row is below M are transformed: the
+// others arrive as zeros (the buffer's out-of-range read / g_hzero4) and stay zeros, so padding is 0 and not
+// relu(shift).  Each register set remembers its K step's channel offset and its four rows' in-range bits for the
+// store two steps later.  Constants: scale / shift of the image of the tile's first row sit in a 4 KB LDS table
+// (Ci <= AFF_TC; filled once per tile, read as four ds_read_b128 per store -- every row of a lane shares its eight
+// channels); a row of another image (a tile that straddles an image boundary: at most one per image when Ho Wo >=
+// 128) or any row when Ci > AFF_TC loads its sixteen constants from global memory in the store instead.  A template
+// parameter again: the AFF = false instances keep their registers, LDS and instructions.
+constexpr int AFF_TC = 512;
+template <bool HIN, int BN, bool BUF = false, bool HOUT = false, bool AFF = false>
 __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
+    static_assert(!AFF || (HIN && H16B_LINES), "operand affine: fp16 operand, whole-line map");
     constexpr int TI = BN == 128 ? 2 : 1, WROWS = BN == 128 ? 64 : 32, NBU = BN == 128 ? 4 : 2;
     __shared__ __attribute__((aligned(16))) _Float16 lds[2][(HBM + BN) * HROW2];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -338,6 +357,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
     int64_t pix[NQ];
     int iy0[NQ], ix0[NQ];
     bool rok[NQ];
+    [[maybe_unused]] int nimg[NQ];  // AFF: the image of row q (its scale / shift row)
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int64_t m = m0 + arow + ARS * q;
@@ -350,6 +370,20 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
         pix[q] = (int64_t)n * a.H * a.W * a.Ci + (LN ? 8 : 4) * aq;
         iy0[q] = oy * a.stride - a.pad;
         ix0[q] = ox * a.stride - a.pad;
+        if constexpr (AFF) nimg[q] = n;
+    }
+    // AFF: the table image (uniform) and its constants, in flight while the first operand loads are issued
+    [[maybe_unused]] float *atab = nullptr;
+    [[maybe_unused]] int ntab = -1;
+    [[maybe_unused]] f32x4 atv = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (AFF) {
+        __shared__ __attribute__((aligned(16))) float aff_tab[2 * AFF_TC];  // [scale | shift][channel]
+        atab = aff_tab;
+        if (a.Ci <= AFF_TC) {
+            ntab = (int)(m0 / ((int64_t)a.Ho * a.Wo));
+            const int c = 4 * (tid & 127);
+            if (c < a.Ci) atv = *(const f32x4 *)((tid < 128 ? a.in_scale : a.in_shift) + (int64_t)ntab * a.Ci + c);
+        }
     }
     // B staging (H16B_LINES): weight rows n0 + (tid >> 3) + 32 u (u < NBU), halves 8 (tid & 7) .. + 7 of the K step
     // (whole 128-B lines per wave load).  Otherwise row n0 + (tid >> 1), halves 32 (tid & 1) .. + 31 (BN 64: row
@@ -380,9 +414,13 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
     f32x4 ra0[8], ra1[8];
     h16x8 rh0[4], rh1[4];  // LN: one 16-B line piece per row q; else pairs of the old map's 8-B quads
     u32x4 rb0[NBU], rb1[NBU];
-#define H16_GLOAD(RA, RH, RB)                                                                              \
+#define H16_GLOAD(RA, RH, RB, RM, RC)                                                                      \
     do {                                                                                                   \
         const int dy = ky * a.dil, dx = kx * a.dil;                                                        \
+        if constexpr (AFF) {                                                                               \
+            RM = 0;                                                                                        \
+            RC = ci0;                                                                                      \
+        }                                                                                                  \
         if constexpr (BUF) {                                                                               \
             const int toff = ((dy * a.W + dx) * a.Ci + ci0) * 2; /* uniform */                             \
             _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                               \
@@ -390,6 +428,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
                 const bool in = rok[q] && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;    \
                 RH[q] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(                   \
                                                       rsx, in ? xrb[q] + toff : (int)0x80000000, 0, 0));   \
+                if constexpr (AFF) RM |= in ? 1 << q : 0;                                                  \
             }                                                                                              \
         } else if constexpr (LN) {                                                                         \
             _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                               \
@@ -397,6 +436,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
                 const bool in = rok[q] && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;    \
                 const int64_t e = pix[q] + ((int64_t)iy * a.W + ix) * a.Ci + ci0;                          \
                 RH[q] = *(const h16x8 *)(in ? a.xh + e : (const _Float16 *)g_hzero4);                      \
+                if constexpr (AFF) RM |= in ? 1 << q : 0;                                                  \
             }                                                                                              \
         } else {                                                                                           \
             _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                \
@@ -435,10 +475,34 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
             }                                                                                              \
         }                                                                                                  \
     } while (0)
-#define H16_SWRITE(BUF, RA, RH, RB)                                                                        \
+#define H16_SWRITE(BUF, RA, RH, RB, RM, RC)                                                                \
     do {                                                                                                   \
         _Float16 *As = lds[BUF], *Bs = As + HBM * HROW2;                                                   \
-        if constexpr (LN) {                                                                                \
+        if constexpr (AFF) {                                                                               \
+            const int c_ = RC + 8 * aq; /* this lane's eight channels of the step in RH */                 \
+            f32x4 ts0 = {0.f, 0.f, 0.f, 0.f}, ts1 = ts0, tt0 = ts0, tt1 = ts0;                             \
+            if (ntab >= 0) {                                                                               \
+                ts0 = *(const f32x4 *)(atab + c_), ts1 = *(const f32x4 *)(atab + c_ + 4);                  \
+                tt0 = *(const f32x4 *)(atab + AFF_TC + c_), tt1 = *(const f32x4 *)(atab + AFF_TC + c_ + 4); \
+            }                                                                                              \
+            _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                               \
+                h16x8 v_ = RH[q];                                                                          \
+                if (RM >> q & 1) { /* in-range tap of a valid row; the others stay the zeros they loaded */ \
+                    f32x4 s0 = ts0, s1 = ts1, t0 = tt0, t1 = tt1;                                          \
+                    if (nimg[q] != ntab) {                                                                 \
+                        const int64_t o_ = (int64_t)nimg[q] * a.Ci + c_;                                   \
+                        s0 = *(const f32x4 *)(a.in_scale + o_), s1 = *(const f32x4 *)(a.in_scale + o_ + 4); \
+                        t0 = *(const f32x4 *)(a.in_shift + o_), t1 = *(const f32x4 *)(a.in_shift + o_ + 4); \
+                    }                                                                                      \
+                    _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                        \
+                        float f_ = (float)v_[e] * (e < 4 ? s0[e & 3] : s1[e & 3]) + (e < 4 ? t0[e & 3] : t1[e & 3]); \
+                        if (a.in_relu) f_ = fmaxf(f_, 0.f);                                                \
+                        v_[e] = (_Float16)f_;                                                              \
+                    }                                                                                      \
+                }                                                                                          \
+                *(h16x8 *)(As + (arow + 32 * q) * HROW2 + 8 * aq) = v_;                                    \
+            }                                                                                              \
+        } else if constexpr (LN) {                                                                         \
             _Pragma("unroll") for (int q = 0; q < NQ; ++q)                                                 \
                 *(h16x8 *)(As + (arow + 32 * q) * HROW2 + 8 * aq) = RH[q];                                 \
         } else {                                                                                           \
@@ -475,33 +539,38 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
         }                                                                                                  \
     } while (0)
     const int nk = a.Kp / HBK2;
-    H16_GLOAD(ra0, rh0, rb0);
-    if (nk > 1) H16_GLOAD(ra1, rh1, rb1);
-    H16_SWRITE(0, ra0, rh0, rb0);
+    [[maybe_unused]] int am0 = 0, am1 = 0, ac0 = 0, ac1 = 0;  // AFF: per register set, in-range bits of its rows / its ci0
+    H16_GLOAD(ra0, rh0, rb0, am0, ac0);
+    if (nk > 1) H16_GLOAD(ra1, rh1, rb1, am1, ac1);
+    if constexpr (AFF) {
+        if (ntab >= 0 && 4 * (tid & 127) < a.Ci) *(f32x4 *)(atab + (tid < 128 ? 0 : AFF_TC) + 4 * (tid & 127)) = atv;
+        __syncthreads();  // the table is complete before the first store reads it
+    }
+    H16_SWRITE(0, ra0, rh0, rb0, am0, ac0);
     __syncthreads();
     int ks = 0;  // loop head: LDS buffer 0 holds step ks, register set 1 step ks + 1
     for (; ks + 3 < nk; ks += 2) {
-        H16_GLOAD(ra0, rh0, rb0);
+        H16_GLOAD(ra0, rh0, rb0, am0, ac0);
         H16_MFMA(0);
-        H16_SWRITE(1, ra1, rh1, rb1);
+        H16_SWRITE(1, ra1, rh1, rb1, am1, ac1);
         __syncthreads();
-        H16_GLOAD(ra1, rh1, rb1);
+        H16_GLOAD(ra1, rh1, rb1, am1, ac1);
         H16_MFMA(1);
-        H16_SWRITE(0, ra0, rh0, rb0);
+        H16_SWRITE(0, ra0, rh0, rb0, am0, ac0);
         __syncthreads();
     }
     if (ks + 2 < nk) {
-        H16_GLOAD(ra0, rh0, rb0);
+        H16_GLOAD(ra0, rh0, rb0, am0, ac0);
         H16_MFMA(0);
-        H16_SWRITE(1, ra1, rh1, rb1);
+        H16_SWRITE(1, ra1, rh1, rb1, am1, ac1);
         __syncthreads();
         H16_MFMA(1);
-        H16_SWRITE(0, ra0, rh0, rb0);
+        H16_SWRITE(0, ra0, rh0, rb0, am0, ac0);
         __syncthreads();
         H16_MFMA(0);
     } else if (ks + 1 < nk) {
         H16_MFMA(0);
-        H16_SWRITE(1, ra1, rh1, rb1);
+        H16_SWRITE(1, ra1, rh1, rb1, am1, ac1);
         __syncthreads();
         H16_MFMA(1);
     } else {
@@ -1085,6 +1154,14 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_h16c(const float *__restrict__
         }
 }
 
+// bev_conv2d_h16_affine's instance: operand affine (fp16 operand), plain fp16 operand, or fp32 operand
+template <int BN, bool BUF, bool HOUT>
+void (*conv_h16_affine_kernel(bool aff, bool x_half))(ConvH) {
+    if (aff) return k_conv_h16b<true, BN, BUF, HOUT, true>;
+    if (x_half) return k_conv_h16b<true, BN, BUF, HOUT>;
+    return k_conv_h16b<false, BN, false, HOUT>;
+}
+
 }  // namespace
 
 namespace bev {
@@ -1092,6 +1169,12 @@ int conv_h16_tune(int value) {
     if (value < 0 || value > 3) return BEV_ERR_ARGS;
     const int old = g_h16_kernel;
     g_h16_kernel = value;
+    return old;
+}
+int conv_h16_buf_tune(int value) {
+    if (value < 0 || value > 1) return BEV_ERR_ARGS;
+    const int old = g_h16_buf;
+    g_h16_buf = value;
     return old;
 }
 }  // namespace bev
@@ -1204,7 +1287,7 @@ static int conv_h16(const void *xv, int x_half, int N, int H, int W, int Ci, con
     if (wide) {
         // 32-bit buffer offsets: operand and panel below 2 GiB (every in-image byte offset, and the out-of-range
         // sentinel 2^31 above them all)
-        const bool buf = H16B_BUF && H16B_LINES && x_half &&
+        const bool buf = H16B_BUF && H16B_LINES && g_h16_buf && x_half &&
                          (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
                          copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
         void (*kern)(ConvH) = n64 ? (x_half ? (buf ? k_conv_h16b<true, 64, true> : k_conv_h16b<true, 64>)
@@ -1250,13 +1333,68 @@ int bev_conv2d_h16_h16(const void *xv, int x_half, int N, int H, int W, int Ci, 
     const bool n64 = (Co <= 64 && g_h16_kernel != 2) || g_h16_kernel == 3;
     const int64_t blocks = ((a.M + HBM - 1) / HBM) * (n64 ? (Co + 63) / 64 : (Co + HBN - 1) / HBN);
     if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
-    const bool buf = H16B_BUF && H16B_LINES && x_half && (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
+    const bool buf = H16B_BUF && H16B_LINES && g_h16_buf && x_half &&
+                     (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
                      copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
     void (*kern)(ConvH) =
         n64 ? (x_half ? (buf ? k_conv_h16b<true, 64, true, true> : k_conv_h16b<true, 64, false, true>)
                       : k_conv_h16b<false, 64, false, true>)
             : (x_half ? (buf ? k_conv_h16b<true, 128, true, true> : k_conv_h16b<true, 128, false, true>)
                       : k_conv_h16b<false, 128, false, true>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int bev_conv2d_h16_affine(const void *xv, int x_half, int N, int H, int W, int Ci, const float *in_scale,
+                          const float *in_shift, int in_relu, const uint16_t *packed, const float *bias, int Co, int KH,
+                          int KW, int stride, int pad, int dilation, int act, void *y, int y_half, int ldy, int Ho,
+                          int Wo, void *stream) {
+    if (!xv || !packed || !y || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
+        pad < 0 || dilation <= 0 || act < 0 || act > 2 || ldy < Co)
+        return BEV_ERR_ARGS;
+    if (Ci % HBK2 != 0) return BEV_ERR_ARGS;  // k_conv_h16b's K step
+    const bool aff = in_scale != nullptr;
+    if ((in_scale == nullptr) != (in_shift == nullptr)) return BEV_ERR_ARGS;
+    if (aff && !x_half) return BEV_ERR_ARGS;  // the affine is applied to the fp16 staging registers
+    if (y_half && (Co % 8 != 0 || ldy != Co)) return BEV_ERR_ARGS;  // dense fp16 rows, 16-B groups of 8 channels
+    if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 ||
+        Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1 || Ho <= 0 || Wo <= 0)
+        return BEV_ERR_ARGS;
+    if ((((uintptr_t)xv | (uintptr_t)packed | (uintptr_t)in_scale | (uintptr_t)in_shift) & 15) != 0)
+        return BEV_ERR_ARGS;
+    if (((uintptr_t)y & (y_half ? 15 : 3)) != 0) return BEV_ERR_ARGS;
+    if (N == 0) return 0;
+    ConvH a;
+    a.x = x_half ? nullptr : (const float *)xv;
+    a.xh = x_half ? (const _Float16 *)xv : nullptr;
+    a.wp = (const _Float16 *)packed;
+    a.bias = bias;
+    a.res = nullptr;
+    a.y = reinterpret_cast<float *>(y);  // fp16 [M][Co] in the HOUT instances
+    a.stats = nullptr;
+    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
+    a.dil = dilation, a.Ho = Ho, a.Wo = Wo, a.act = act, a.ldy = ldy;
+    a.Kp = (int)kpad_h(Ci * KH * KW);
+    a.M = (int64_t)N * Ho * Wo;
+    a.in_scale = in_scale, a.in_shift = in_shift, a.in_relu = in_relu;
+    // tile widths as in conv_h16 (CONV_H16_KERNEL 2 / 3 force one; 1 has no form of this kernel and runs as 0)
+    const bool n64 = (Co <= 64 && g_h16_kernel != 2) || g_h16_kernel == 3;
+    const int64_t blocks = ((a.M + HBM - 1) / HBM) * (n64 ? (Co + 63) / 64 : (Co + HBN - 1) / HBN);
+    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
+    const bool buf = H16B_BUF && H16B_LINES && g_h16_buf && x_half &&
+                     (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
+                     copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
+    void (*kern)(ConvH);
+    if (n64)
+        kern = y_half ? (buf ? conv_h16_affine_kernel<64, true, true>(aff, x_half)
+                             : conv_h16_affine_kernel<64, false, true>(aff, x_half))
+                      : (buf ? conv_h16_affine_kernel<64, true, false>(aff, x_half)
+                             : conv_h16_affine_kernel<64, false, false>(aff, x_half));
+    else
+        kern = y_half ? (buf ? conv_h16_affine_kernel<128, true, true>(aff, x_half)
+                             : conv_h16_affine_kernel<128, false, true>(aff, x_half))
+                      : (buf ? conv_h16_affine_kernel<128, true, false>(aff, x_half)
+                             : conv_h16_affine_kernel<128, false, false>(aff, x_half));
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

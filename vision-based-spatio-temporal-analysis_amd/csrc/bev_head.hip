@@ -28,25 +28,36 @@ constexpr int GN_T = 256;
 // partials in parallel (one workgroup per (image, group) / per 16 channels) instead of one thread per output.
 constexpr int GN_PIX_PER_BLOCK = 512;
 
-// thread -> (channel quad q, pixel phase): QP = C / 4 quads per pixel, 256 % QP == 0
-__global__ __launch_bounds__(GN_T) void k_gn_partial(const float *__restrict__ x, int64_t P, int C, int G,
+// 4 stored values in: fp32 (16-B load), or fp16 (8-B load, each half converted exactly)
+__device__ __forceinline__ float4 gn_ld4(const float *p) { return *(const float4 *)p; }
+__device__ __forceinline__ float4 gn_ld4(const _Float16 *p) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    const h4 v = *(const h4 *)p;
+    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+
+// thread -> (channel quad q, pixel phase): QP = C / 4 quads per pixel, 256 % QP == 0.  XT: the stored type of x
+// (float, or _Float16 for the "f16" head's conv outputs): same thread map, blocks and summation order, so the fp16
+// instance gives bitwise the fp32 instance's partials on the upcast map.
+template <typename XT>
+__global__ __launch_bounds__(GN_T) void k_gn_partial(const XT *__restrict__ x, int64_t P, int C, int G,
                                                      double *__restrict__ part /* [N][nb][G][2] */) {
     __shared__ double red[GN_T][2];
     const int n = blockIdx.y, nb = gridDim.x, blk = blockIdx.x, tid = threadIdx.x;
     const int QP = C / 4, q = tid % QP, ph = tid / QP, nph = GN_T / QP;
     const int64_t p0 = (int64_t)blk * GN_PIX_PER_BLOCK, p1 = p0 + GN_PIX_PER_BLOCK < P ? p0 + GN_PIX_PER_BLOCK : P;
-    const float *xb = x + (size_t)n * P * C;
+    const XT *xb = x + (size_t)n * P * C;
     double s0 = 0.0, ss0 = 0.0, s1 = 0.0, ss1 = 0.0;  // two independent chains (pixels p, p + nph)
     int64_t p = p0 + ph;
     for (; p + nph < p1; p += 2 * nph) {
-        const float4 v = *(const float4 *)(xb + p * C + 4 * q), w = *(const float4 *)(xb + (p + nph) * C + 4 * q);
+        const float4 v = gn_ld4(xb + p * C + 4 * q), w = gn_ld4(xb + (p + nph) * C + 4 * q);
         s0 += (double)v.x + (double)v.y + (double)v.z + (double)v.w;
         ss0 += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
         s1 += (double)w.x + (double)w.y + (double)w.z + (double)w.w;
         ss1 += (double)w.x * w.x + (double)w.y * w.y + (double)w.z * w.z + (double)w.w * w.w;
     }
     if (p < p1) {
-        const float4 v = *(const float4 *)(xb + p * C + 4 * q);
+        const float4 v = gn_ld4(xb + p * C + 4 * q);
         s0 += (double)v.x + (double)v.y + (double)v.z + (double)v.w;
         ss0 += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
     }
@@ -474,18 +485,28 @@ int64_t bev_groupnorm_workspace_bytes(int N, int64_t P, int C, int G) {
     return (int64_t)N * nb * (G + C) * 2 * (int64_t)sizeof(double) + (int64_t)N * G * 2 * (int64_t)sizeof(float);
 }
 
-int bev_groupnorm_fwd_f32(const float *x, int N, int64_t P, int C, int G, float eps, const float *gamma,
-                          const float *beta, float *mean, float *rstd, float *scale, float *shift, void *workspace,
-                          void *stream) {
+int bev_groupnorm_fwd_ex_f32(const void *x, int x_half, int N, int64_t P, int C, int G, float eps, const float *gamma,
+                             const float *beta, float *mean, float *rstd, float *scale, float *shift, void *workspace,
+                             void *stream) {
     if (!x || !gamma || !beta || !mean || !rstd || !scale || !shift || !workspace || !gn_shape_ok(N, P, C, G))
         return BEV_ERR_ARGS;
+    if (x_half && ((uintptr_t)x & 7) != 0) return BEV_ERR_ARGS;
     hipStream_t st = (hipStream_t)stream;
     const int nb = nblocks(P);
     double *part = (double *)workspace;
-    hipLaunchKernelGGL(k_gn_partial, dim3(nb, N), dim3(GN_T), 0, st, x, P, C, G, part);
+    if (x_half)
+        hipLaunchKernelGGL(k_gn_partial<_Float16>, dim3(nb, N), dim3(GN_T), 0, st, (const _Float16 *)x, P, C, G, part);
+    else
+        hipLaunchKernelGGL(k_gn_partial<float>, dim3(nb, N), dim3(GN_T), 0, st, (const float *)x, P, C, G, part);
     hipLaunchKernelGGL(k_gn_finalize, dim3(N * G), dim3(GN_T), 0, st, part, nb, P, C, G, eps, gamma, beta, mean, rstd,
                        scale, shift);
     return (int)hipGetLastError();
+}
+
+int bev_groupnorm_fwd_f32(const float *x, int N, int64_t P, int C, int G, float eps, const float *gamma,
+                          const float *beta, float *mean, float *rstd, float *scale, float *shift, void *workspace,
+                          void *stream) {
+    return bev_groupnorm_fwd_ex_f32(x, 0, N, P, C, G, eps, gamma, beta, mean, rstd, scale, shift, workspace, stream);
 }
 
 int bev_groupnorm_apply_ex_f32(const float *x, int N, int64_t P, int C, const float *scale, const float *shift,

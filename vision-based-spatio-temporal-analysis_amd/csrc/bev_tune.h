@@ -19,6 +19,8 @@ int conv_x6_tune(int knob, int value);
 
 // BEV_TUNE_CONV_H16_KERNEL (bev_conv_h16.hip).
 int conv_h16_tune(int value);
+// BEV_TUNE_CONV_H16_BUF (bev_conv_h16.hip).
+int conv_h16_buf_tune(int value);
 
 // BEV_TUNE_DW_RUN (bev_effnet.hip).
 int dw_tune(int value);

@@ -13,6 +13,9 @@ The computation is native and channels-last:
   applied by the NEXT conv while it loads its operand -- the 512- and 128-channel normalised maps are
   never written;
 * the three heads are ONE 128 -> 5 conv (weights concatenated), split into the reference's outputs;
+* opt-in, inference only (bev_native.head_arith_mode("f16")): the same graph on the fp16 matrix cores, as the
+  reference's validation forward under autocast(float16) -- fp16-stored conv outputs, GroupNorm statistics of the
+  stored values, the affine + ReLU in the next conv's operand loader (bev_conv2d_h16_affine), fp32 outputs;
 * training materialises each GroupNorm + ReLU output and runs the native backward (conv dgrad as a
   conv with the flipped, transposed kernel; dilated wgrad; GroupNorm backward kernels).
 * decode: bev_decode_peaks_f32 + bev_decode_nms_f32 (peak test, threshold, sort, greedy NMS on the
@@ -39,19 +42,21 @@ def _ceil_to(c: int, m: int) -> int:
 
 class _Packed:
     """Packed MFMA panel of a conv weight (input channels zero-padded to `cin_pad`), rebuilt when the
-    parameter changes (storage pointer + version counter)."""
+    parameter changes (storage pointer + version counter).  `mode`: the head arithmetic the slot serves ("f32": the
+    exact-f32 panel, "f16": the fp16 panel); it is part of the key, and each mode has its own slots."""
 
-    def __init__(self):
-        self.key, self.panel = None, None
+    def __init__(self, mode: str = "f32"):
+        self.mode, self.key, self.panel = mode, None, None
 
     def get(self, weight: torch.Tensor, cin_pad: int) -> torch.Tensor:
-        key = (weight.data_ptr(), weight._version, cin_pad, str(weight.device))
+        key = (self.mode, weight.data_ptr(), weight._version, cin_pad, str(weight.device))
         if key != self.key:
             with torch.no_grad():
                 w = weight.detach().float()
                 if cin_pad > w.shape[1]:
                     w = F.pad(w, (0, 0, 0, 0, 0, cin_pad - w.shape[1]))
-                self.panel = _nat.pack_conv_weight(w.contiguous())
+                pack = _nat.pack_conv_weight_h16 if self.mode == "f16" else _nat.pack_conv_weight
+                self.panel = pack(w.contiguous())
             self.key = key
         return self.panel
 
@@ -232,6 +237,8 @@ class BEVDetector(nn.Module):
         with torch.no_grad():
             self.size_head.bias.copy_(torch.log(torch.tensor(cells, dtype=torch.float32)))
         self._panels = [_Packed() for _ in range(3)]
+        self._panels_f16 = [_Packed("f16") for _ in range(3)]  # the "f16" head arithmetic's stem panels
+        self._heads_f16 = (None, None, None)                   # ... and its 128 -> 5 panel and bias: (key, panel, bias)
         self.h16_node = True  # AMP training: the head as one node with fp16-stored inner tensors (bit-identical)
 
     # ---- layout helpers -----------------------------------------------------------------------
@@ -239,6 +246,16 @@ class BEVDetector(nn.Module):
     def input_channels_padded(self) -> int:
         """Channel count of the NHWC operand forward_nhwc expects (in_channels rounded up to 32)."""
         return _ceil_to(self.in_channels, 32)
+
+    def _train_path(self) -> bool:
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def operand_channels(self) -> int:
+        """Channel count of the NHWC operand the forward that would run now reads without a copy: in_channels
+        rounded up to 64 for the "f16" inference arithmetic (bev_native.head_arith), else input_channels_padded."""
+        if not self._train_path() and _nat.head_arith() == "f16":
+            return _ceil_to(self.in_channels, 64)
+        return self.input_channels_padded
 
     def _convs(self):
         return (self.stem[0], self.stem[3], self.stem[6]), (self.stem[1], self.stem[4], self.stem[7])
@@ -253,14 +270,15 @@ class BEVDetector(nn.Module):
         """bev_feat [B, in_channels, H, W] (any strides) -> heatmap_logits / heatmap [B,1,H,W],
         offset(_raw) / size(_raw) [B,2,H,W]."""
         B, C, H, W = bev_feat.shape
-        x = torch.zeros(B, H, W, self.input_channels_padded, device=bev_feat.device, dtype=torch.float32)
+        x = torch.zeros(B, H, W, self.operand_channels(), device=bev_feat.device, dtype=torch.float32)
         x[..., :C] = bev_feat.permute(0, 2, 3, 1)
         return self.forward_nhwc(x)
 
     def forward_nhwc(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """x [B, H, W, input_channels_padded] NHWC (channels >= in_channels zero)."""
+        """x [B, H, W, input_channels_padded] NHWC (channels >= in_channels zero); the "f16" inference arithmetic
+        reads operand_channels() channels and zero-pads a narrower operand with a copy."""
         convs, gns = self._convs()
-        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        train = self._train_path()
         if train and self.h16_node and _head_h16_ok(self):  # AMP: one node, fp16-stored inner tensors (bit-identical)
             w, b = self._head_params()
             (c1, c2, c3), (n1, n2, n3) = convs, gns
@@ -273,6 +291,9 @@ class BEVDetector(nn.Module):
                 a = _GroupNormReLU.apply(z, gn.weight, gn.bias, gn.eps)
             w, b = self._head_params()
             y = _HeadConv.apply(a, w, b, 1)
+        elif _nat.head_arith() == "f16":
+            with torch.no_grad():
+                y = self._forward_f16(x)
         else:
             with torch.no_grad():
                 z, scale, shift = x, None, None
@@ -292,6 +313,33 @@ class BEVDetector(nn.Module):
         size_raw = y[..., 3:5].permute(0, 3, 1, 2).contiguous()
         return {"heatmap_logits": logits, "heatmap": torch.sigmoid(logits), "offset": torch.sigmoid(offset_raw),
                 "offset_raw": offset_raw, "size": torch.exp(size_raw), "size_raw": size_raw}
+
+    def _forward_f16(self, x: torch.Tensor) -> torch.Tensor:
+        """The eval head in the "f16" arithmetic -> y [B, H, W, 5] fp32.  z_i = f16(conv(a_{i-1})) on the fp16 matrix
+        cores (fp32 accumulation; the fp32 operand x is rounded while conv1 stages it), GroupNorm statistics from the
+        stored fp16 z_i, a_i = f16(relu(z_i * scale + shift)) formed in the next conv's operand loader, the 5-channel
+        conv's output fp32 and not rounded."""
+        convs, gns = self._convs()
+        if x.shape[-1] % 64 != 0:  # e.g. the input_channels_padded-wide operand: zero-pad to the fp16 kernel's K step
+            xz = x.new_zeros(*x.shape[:3], _ceil_to(x.shape[-1], 64))
+            xz[..., :x.shape[-1]] = x
+            x = xz
+        z, scale, shift = x.float(), None, None
+        for i, (conv, gn) in enumerate(zip(convs, gns)):
+            d = conv.dilation[0]
+            panel = self._panels_f16[i].get(conv.weight, z.shape[-1])
+            z = _nat.conv2d_h16_affine(z, panel, None, conv.out_channels, 3, d, d, in_scale=scale, in_shift=shift,
+                                       in_relu=scale is not None, y_half=True)
+            _, _, scale, shift = _nat.groupnorm_fwd(z, _GROUPS, gn.weight, gn.bias, gn.eps)
+        heads = (self.heatmap_head, self.offset_head, self.size_head)
+        key = tuple((t.data_ptr(), t._version, str(t.device)) for h in heads for t in (h.weight, h.bias))
+        if key != self._heads_f16[0]:
+            w, b = self._head_params()
+            self._heads_f16 = (key, _nat.pack_conv_weight_h16(w.detach().float().contiguous()),
+                               b.detach().float().contiguous())
+        _, panel, b = self._heads_f16
+        return _nat.conv2d_h16_affine(z, panel, b, 5, 3, 1, 1, in_scale=scale, in_shift=shift, in_relu=True,
+                                      y_half=False)
 
     # ---- decode (detector.py:64-125) ------------------------------------------------------------
     @staticmethod

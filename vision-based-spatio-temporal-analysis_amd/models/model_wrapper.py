@@ -15,8 +15,8 @@ The computation is reorganised for the GPU:
   conv over Hf*Wf pixels instead of Hb*Wb cells) and the V projected maps are warped and summed by ONE fused
   kernel (bev_ipm_warp_fuse_f32, mode "sum") -- the [B, V*C, Hb, Wb] tensor is never formed.  Same value up
   to fp32 reassociation (the BEVNet parity test pins it against the reference's own outputs).
-* The head input is assembled channels-last ([B, Hb, Wb, ceil32(P+2)]: projection, pos-enc, zero pad) and
-  fed to BEVDetector.forward_nhwc; `bev_feat` is returned as an NCHW view of it.
+* The head input is assembled channels-last ([B, Hb, Wb, ceil32(P+2)], ceil64 for the "f16" inference head:
+  projection, pos-enc, zero pad) and fed to BEVDetector.forward_nhwc; `bev_feat` is returned as an NCHW view of it.
 * Training targets are built for the whole batch at once (no per-object Python loop / host syncs): gaussian
   splats are one scatter_reduce('amax') over every object's footprint.
 """
@@ -263,7 +263,7 @@ class BEVNet(nn.Module):
             self.detector = BEVDetector(in_channels=P + 2, bev_bounds=self.bounds, bev_size=(self.bev_h, self.bev_w),
                                         default_box_wh=self.default_box_wh).to(main.device)
         self.detector.grad_channels = P  # the position-encoding channels are a buffer: no gradient
-        cp = self.detector.input_channels_padded
+        cp = self.detector.operand_channels()  # input_channels_padded; ceil64 for the "f16" inference head
         if bias is not None and P <= 512 and main.is_cuda:
             x = _HeadOperand.apply(main, bias, self.pos_enc, cp)  # [B, Hb, Wb, cp] channels-last head operand
         else:
