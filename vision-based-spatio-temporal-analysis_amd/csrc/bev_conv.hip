@@ -72,36 +72,36 @@ __device__ __forceinline__ float act_fn(float t, int act) {
     return t > 0.0f ? t : 0.0f;
 }
 
-struct ConvArgs {
-    const float *__restrict__ x;
-    const float *__restrict__ wp;
-    const float *__restrict__ bias;
-    const float *__restrict__ res;
-    float *__restrict__ y;
-    int N, H, W, Ci, Co, KH, KW, stride, pad, Ho, Wo;
-    int relu;
-    int in_nchw;  // generic loader only: input is NCHW instead of NHWC
-    int64_t M;
-    int K;
-    int Kp;
+struct ConvArgs {  // conv_args fills the geometry; an entry point sets what is particular to it over these defaults
+    const float *__restrict__ x = nullptr;
+    const float *__restrict__ wp = nullptr;
+    const float *__restrict__ bias = nullptr;
+    const float *__restrict__ res = nullptr;
+    float *__restrict__ y = nullptr;
+    int N = 0, H = 0, W = 0, Ci = 0, Co = 0, KH = 0, KW = 0, stride = 0, pad = 0, Ho = 0, Wo = 0;
+    int relu = 0;
+    int in_nchw = 0;  // generic loader only: input is NCHW instead of NHWC
+    int64_t M = 0;
+    int K = 0;
+    int Kp = 0;
     // dual-source 1x1 (LOADER 3): k in [Ci, Ci + Ci2) reads x2 [N][H2][W2][Ci2] at (oy*s2, ox*s2)
-    const float *__restrict__ x2;
-    int Ci2, H2, W2, stride2;
+    const float *__restrict__ x2 = nullptr;
+    int Ci2 = 0, H2 = 0, W2 = 0, stride2 = 0;
     // per-(image, input channel) multiplier of the A operand (SqueezeExcite excitation folded into
     // the projection conv's loader: conv(x * gate)); NULL = none.  Fast and contiguous loaders only.
-    const float *__restrict__ ascale;
+    const float *__restrict__ ascale = nullptr;
     // with ascale: per-(image, input channel) shift added after the scale, then ReLU when arelu
     // (a GroupNorm + ReLU of the previous layer applied on the fly; out-of-range taps stay 0)
-    const float *__restrict__ ashift;
-    int arelu;
-    int dil;  // dilation of the taps (input offset ky * dil, kx * dil)
-    int ldy;  // row stride of y in floats (>= Co; a channel slice of a wider NHWC buffer)
-    int xcd;  // 1: XCD-aware block order (the N tiles of one M block run on one XCD, sharing its L2)
+    const float *__restrict__ ashift = nullptr;
+    int arelu = 0;
+    int dil = 1;  // dilation of the taps (input offset ky * dil, kx * dil)
+    int ldy = 0;  // row stride of y in floats (>= Co; a channel slice of a wider NHWC buffer)
+    int xcd = 0;  // 1: XCD-aware block order (the N tiles of one M block run on one XCD, sharing its L2)
     // chained pointwise conv (EPI 1, bev_conv2d_chain_f32): y = act2(h (*) W2 + bias2 + res), h = this conv's output
-    const float *__restrict__ wp2;
-    const float *__restrict__ bias2;
-    int Co2, Kp2, relu2;
-    int pwvec;  // k_pw_mfma: float4 epilogue through LDS (set by try_pw_mfma)
+    const float *__restrict__ wp2 = nullptr;
+    const float *__restrict__ bias2 = nullptr;
+    int Co2 = 0, Kp2 = 0, relu2 = 0;
+    int pwvec = 0;  // k_pw_mfma: float4 epilogue through LDS (set by try_pw_mfma)
 };
 
 // Per-thread view of the A tile rows it loads: rows (tid >> 3) + 32 r, one 16-B quad.
@@ -1506,6 +1506,22 @@ int launch_chain(const ConvArgs &a, hipStream_t st) {
     return last();
 }
 
+// The geometry every entry point passes on (K = Ci KH KW); what is particular to one (in_nchw, the x2 block and its
+// K, the operand affine, the chained conv) it sets itself.
+ConvArgs conv_args(const float *x, const float *packed, const float *bias, const float *res, float *y, int N, int H,
+                   int W, int Ci, int Co, int KH, int KW, int stride, int pad, int dil, int Ho, int Wo, int relu,
+                   int ldy) {
+    ConvArgs a;
+    a.x = x, a.wp = packed, a.bias = bias, a.res = res, a.y = y;
+    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
+    a.dil = dil, a.Ho = Ho, a.Wo = Wo, a.relu = relu, a.ldy = ldy;
+    a.M = (int64_t)N * Ho * Wo;
+    a.K = Ci * KH * KW;
+    a.Kp = (int)kpad(a.K);
+    a.xcd = conv_xcd();
+    return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1604,27 +1620,7 @@ static int conv2d_impl(const float *x, int in_nchw, int N, int H, int W, int Ci,
         Ho <= 0 || Wo <= 0)
         return BEV_ERR_ARGS;
     if (N == 0) return 0;
-    ConvArgs a;
-    a.x = x;
-    a.wp = packed;
-    a.bias = bias;
-    a.res = residual;
-    a.y = y;
-    a.N = N;
-    a.H = H;
-    a.W = W;
-    a.Ci = Ci;
-    a.Co = Co;
-    a.KH = KH;
-    a.KW = KW;
-    a.stride = stride;
-    a.pad = pad;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.relu = relu;
-    a.M = (int64_t)N * Ho * Wo;
-    a.K = Ci * KH * KW;
-    a.Kp = (int)kpad(a.K);
+    ConvArgs a = conv_args(x, packed, bias, residual, y, N, H, W, Ci, Co, KH, KW, stride, pad, dil, Ho, Wo, relu, ldy);
     a.in_nchw = in_nchw;
     const bool pw = !in_nchw && KH == 1 && KW == 1 && stride == 1 && pad == 0 && Ci % 4 == 0 &&
                     ((uintptr_t)x & 15) == 0;
@@ -1632,14 +1628,9 @@ static int conv2d_impl(const float *x, int in_nchw, int N, int H, int W, int Ci,
     if (loader == 1 && (ashift || arelu || dil != 1)) loader = 5;
     else if (loader == 1 && ascale) loader = 6;
     if ((ashift || arelu) && loader != 5) return BEV_ERR_ARGS;
-    a.x2 = nullptr;
-    a.Ci2 = a.H2 = a.W2 = a.stride2 = 0;
     a.ascale = ascale;
     a.ashift = ashift;
     a.arelu = arelu;
-    a.dil = dil;
-    a.ldy = ldy;
-    a.xcd = conv_xcd();
     if (in_nchw && Ci == 3 && KH == 7 && KW == 7 && stride == 2 && pad == 3 && Co <= 64 && !residual && bias &&
         g_conv_tile == 0 && relu <= 1 && !ascale && dil == 1 && ldy == Co)
         return launch_stem(x, N, H, W, packed, a.Kp, bias, Co, y, Ho, Wo, relu, (hipStream_t)stream);
@@ -1655,44 +1646,25 @@ int bev_conv2d_dual_f32(const float *x, int N, int Ho, int Wo, int Ci, const flo
     if (Ci % BK != 0 || Ci2 % BK != 0) return BEV_ERR_ARGS;
     if (Ho != (H2 - 1) / stride2 + 1 || Wo != (W2 - 1) / stride2 + 1) return BEV_ERR_ARGS;
     if (N == 0) return 0;
-    ConvArgs a;
-    a.x = x;
-    a.wp = packed;
-    a.bias = bias;
-    a.res = nullptr;
-    a.y = y;
-    a.N = N;
-    a.H = Ho;
-    a.W = Wo;
-    a.Ci = Ci;
-    a.Co = Co;
-    a.KH = a.KW = 1;
-    a.stride = 1;
-    a.pad = 0;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.relu = relu;
-    a.M = (int64_t)N * Ho * Wo;
+    ConvArgs a = conv_args(x, packed, bias, nullptr, y, N, Ho, Wo, Ci, Co, 1, 1, 1, 0, 1, Ho, Wo, relu, Co);
     a.K = Ci + Ci2;
     a.Kp = (int)kpad(a.K);
-    a.in_nchw = 0;
     a.x2 = x2;
-    a.ascale = nullptr;
-    a.ashift = nullptr;
-    a.arelu = 0;
-    a.dil = 1;
-    a.ldy = Co;
-    a.xcd = conv_xcd();
-    a.Ci2 = Ci2;
-    a.H2 = H2;
-    a.W2 = W2;
-    a.stride2 = stride2;
+    a.Ci2 = Ci2, a.H2 = H2, a.W2 = W2, a.stride2 = stride2;
     return launch_tiled(a, 3, (hipStream_t)stream);
 }
 
-int bev_conv2d_chain_f32(const float *x, int N, int H, int W, int Ci, const float *packed, const float *bias, int Co,
-                         int KH, int KW, int stride, int pad, int relu, const float *packed2, const float *bias2,
-                         int Co2, const float *residual, int relu2, float *y, int Ho, int Wo, void *stream) {
+// Both chain entry points: x2 (the dual form's shortcut operand, conv3's K continued over it) or none.
+static int chain_impl(const float *x, int N, int H, int W, int Ci, const float *packed, const float *bias, int Co,
+                      int KH, int KW, int stride, int pad, int relu, bool dual, const float *x2, int H2, int W2,
+                      int Ci2, int stride2, const float *packed2, const float *bias2, int Co2, const float *residual,
+                      int relu2, float *y, int Ho, int Wo, void *stream) {
+    if (dual) {
+        if (!x2 || Ci2 <= 0 || Ci2 % BK != 0 || H2 <= 0 || W2 <= 0 || stride2 <= 0 || ((uintptr_t)x2 & 15) != 0)
+            return BEV_ERR_ARGS;
+        if (Ho != (H2 - 1) / stride2 + 1 || Wo != (W2 - 1) / stride2 + 1) return BEV_ERR_ARGS;
+        if ((int64_t)N * H2 * W2 * Ci2 * 4 > (int64_t)0xffffffff) return BEV_ERR_ARGS;  // 32-bit buffer offsets
+    }
     if (!x || !packed || !packed2 || !y || N < 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
         pad < 0 || relu < 0 || relu > 2 || relu2 < 0 || relu2 > 2)
         return BEV_ERR_ARGS;
@@ -1702,93 +1674,32 @@ int bev_conv2d_chain_f32(const float *x, int N, int H, int W, int Ci, const floa
     if (Ho != (H + 2 * pad - KH) / stride + 1 || Wo != (W + 2 * pad - KW) / stride + 1 || Ho <= 0 || Wo <= 0)
         return BEV_ERR_ARGS;
     if (N == 0) return 0;
-    ConvArgs a{};
-    a.x = x;
-    a.wp = packed;
-    a.bias = bias;
-    a.res = residual;
-    a.y = y;
-    a.N = N;
-    a.H = H;
-    a.W = W;
-    a.Ci = Ci;
-    a.Co = Co;
-    a.KH = KH;
-    a.KW = KW;
-    a.stride = stride;
-    a.pad = pad;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.relu = relu;
-    a.M = (int64_t)N * Ho * Wo;
-    a.K = Ci * KH * KW;
-    a.Kp = (int)kpad(a.K);
-    a.dil = 1;
-    a.ldy = Co2;
-    a.xcd = conv_xcd();
+    ConvArgs a = conv_args(x, packed, bias, residual, y, N, H, W, Ci, Co, KH, KW, stride, pad, 1, Ho, Wo, relu, Co2);
     a.wp2 = packed2;
     a.bias2 = bias2;
     a.Co2 = Co2;
-    a.Kp2 = (int)kpad(Co);
+    a.Kp2 = (int)kpad(Co + (dual ? Ci2 : 0));
     a.relu2 = relu2;
-    a.x2 = nullptr;
-    a.Ci2 = a.H2 = a.W2 = a.stride2 = 0;
+    if (dual) {
+        a.x2 = x2;
+        a.Ci2 = Ci2, a.H2 = H2, a.W2 = W2, a.stride2 = stride2;
+    }
     return launch_chain(a, (hipStream_t)stream);
+}
+
+int bev_conv2d_chain_f32(const float *x, int N, int H, int W, int Ci, const float *packed, const float *bias, int Co,
+                         int KH, int KW, int stride, int pad, int relu, const float *packed2, const float *bias2,
+                         int Co2, const float *residual, int relu2, float *y, int Ho, int Wo, void *stream) {
+    return chain_impl(x, N, H, W, Ci, packed, bias, Co, KH, KW, stride, pad, relu, false, nullptr, 0, 0, 0, 0, packed2,
+                      bias2, Co2, residual, relu2, y, Ho, Wo, stream);
 }
 
 int bev_conv2d_chain_dual_f32(const float *x, int N, int H, int W, int Ci, const float *packed, const float *bias,
                               int Co, int KH, int KW, int stride, int pad, int relu, const float *x2, int H2, int W2,
                               int Ci2, int stride2, const float *packed2, const float *bias2, int Co2, int relu2,
                               float *y, int Ho, int Wo, void *stream) {
-    if (!x2 || Ci2 <= 0 || Ci2 % BK != 0 || H2 <= 0 || W2 <= 0 || stride2 <= 0 || ((uintptr_t)x2 & 15) != 0)
-        return BEV_ERR_ARGS;
-    if (Ho != (H2 - 1) / stride2 + 1 || Wo != (W2 - 1) / stride2 + 1) return BEV_ERR_ARGS;
-    if ((int64_t)N * H2 * W2 * Ci2 * 4 > (int64_t)0xffffffff) return BEV_ERR_ARGS;  // 32-bit buffer offsets
-    // validate / fill the common part through the plain entry point's checks, then launch with x2
-    if (!x || !packed || !packed2 || !y || N < 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
-        pad < 0 || relu < 0 || relu > 2 || relu2 < 0 || relu2 > 2)
-        return BEV_ERR_ARGS;
-    if (Ci % BK != 0 || (Co != 64 && Co != 128) || Co2 <= 0 || Co2 % 128 != 0 || ((uintptr_t)x & 15) != 0 ||
-        (((uintptr_t)packed | (uintptr_t)packed2) & 15) != 0)
-        return BEV_ERR_ARGS;
-    if (Ho != (H + 2 * pad - KH) / stride + 1 || Wo != (W + 2 * pad - KW) / stride + 1 || Ho <= 0 || Wo <= 0)
-        return BEV_ERR_ARGS;
-    if (N == 0) return 0;
-    ConvArgs a{};
-    a.x = x;
-    a.wp = packed;
-    a.bias = bias;
-    a.res = nullptr;
-    a.y = y;
-    a.N = N;
-    a.H = H;
-    a.W = W;
-    a.Ci = Ci;
-    a.Co = Co;
-    a.KH = KH;
-    a.KW = KW;
-    a.stride = stride;
-    a.pad = pad;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.relu = relu;
-    a.M = (int64_t)N * Ho * Wo;
-    a.K = Ci * KH * KW;
-    a.Kp = (int)kpad(a.K);
-    a.dil = 1;
-    a.ldy = Co2;
-    a.xcd = conv_xcd();
-    a.wp2 = packed2;
-    a.bias2 = bias2;
-    a.Co2 = Co2;
-    a.Kp2 = (int)kpad(Co + Ci2);
-    a.relu2 = relu2;
-    a.x2 = x2;
-    a.Ci2 = Ci2;
-    a.H2 = H2;
-    a.W2 = W2;
-    a.stride2 = stride2;
-    return launch_chain(a, (hipStream_t)stream);
+    return chain_impl(x, N, H, W, Ci, packed, bias, Co, KH, KW, stride, pad, relu, true, x2, H2, W2, Ci2, stride2,
+                      packed2, bias2, Co2, nullptr, relu2, y, Ho, Wo, stream);
 }
 
 // The same pooling with a (pixel-row-piece, output row, image) grid: 32-bit index arithmetic (the flat kernel's
