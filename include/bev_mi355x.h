@@ -65,9 +65,10 @@ const char *bev_build_source_hash(void);
  *   wherever Ci (and Ci2) % 32 == 0, 1 = the 16-deep-step kernel (both operands through LDS) for every shape.
  *   Same results bit for bit.
  * BEV_TUNE_CONV_H16_KERNEL: autocast fp16 convs: 0 (default) = 64-deep K steps, two steps in flight, where Ci % 64 ==
- *   0 (64-column tiles for Co <= 64), and the 64-pixel-step weight gradient; 1 = the 32-deep-step conv and
- *   32-pixel-step weight gradient always; 2 = as 0 with 128-column tiles always.  Same conv results bit for bit;
- *   weight gradients equal to fp32 tolerance (pixel chunks differ).
+ *   0 (64-column tiles for Co <= 64), and the transposing-LDS-read weight gradient where Ci, Co % 8 == 0; 1 = the
+ *   32-deep-step conv (fp32 operands, fp32 output, no statistics) and the register-transpose weight gradient always;
+ *   2 = as 0 with 128-column tiles always; 3 = as 0 with 64-column tiles always.  Same conv results bit for bit;
+ *   weight gradients equal to fp32 tolerance (the order of the float atomics varies).
  * BEV_TUNE_CONV_H16_BUF: fp16-stored operands of the fp16 convs: 1 (default) = staged by raw buffer loads with 32-bit
  *   offsets where the operand and the panel are below 2 GiB, 0 = by 64-bit pointers always (the form larger operands
  *   take).  Same results bit for bit.

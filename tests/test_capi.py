@@ -91,6 +91,96 @@ def test_argument_validation_without_gpu(lib):
     assert lib.bev_homography_f32(null, null, 0, null, null) == 0
 
 
+# Argument order of the five fp16 forward conv entry points (include/bev_mi355x.h) and one accepted argument set.
+# N = 0 in every row: the library answers (0 or BEV_ERR_ARGS) before any HIP call, so the made-up addresses are
+# never handed to a kernel.
+_H16_ORDER = {
+    "bev_conv2d_h16_f32": "x N H W Ci packed bias residual Co KH KW stride pad dilation act y ldy Ho Wo stream",
+    "bev_conv2d_h16_bnstats_f32": "x N H W Ci packed bias Co KH KW stride pad dilation y Ho Wo tile_stats stream",
+    "bev_conv2d_h16_ex_f32": "x x_half N H W Ci packed bias residual Co KH KW stride pad dilation act y ldy Ho Wo "
+                             "tile_stats stream",
+    "bev_conv2d_h16_h16": "x x_half N H W Ci packed bias residual Co KH KW stride pad dilation act y Ho Wo stream",
+    "bev_conv2d_h16_affine": "x x_half N H W Ci in_scale in_shift in_relu packed bias Co KH KW stride pad dilation act "
+                             "y y_half ldy Ho Wo stream",
+}
+_H16_BASE = dict(x=0x10000, x_half=1, N=0, H=8, W=8, Ci=64, packed=0x20000, bias=None, residual=None, Co=64, KH=3, KW=3,
+                 stride=1, pad=1, dilation=1, act=0, y=0x30000, y_half=1, ldy=64, Ho=8, Wo=8, tile_stats=None,
+                 in_scale=None, in_shift=None, in_relu=0, stream=None)
+_H16_F32 = ("bev_conv2d_h16_f32", "bev_conv2d_h16_bnstats_f32", "bev_conv2d_h16_ex_f32")
+_H16_COMMON = [  # one rule violated -> -1 from every entry that has the argument
+    dict(x=None), dict(packed=None), dict(y=None), dict(N=-1), dict(H=0), dict(W=0), dict(Ci=0), dict(Co=0), dict(KH=0),
+    dict(KW=0), dict(stride=0), dict(dilation=0), dict(pad=-1), dict(act=-1), dict(act=3),
+    dict(Ho=7), dict(Wo=9), dict(stride=2),          # Ho / Wo inconsistent with the geometry
+    dict(H=1, pad=0, Ho=-1, Wo=6),                   # consistent, but no output row
+    dict(x=0x10008), dict(packed=0x20008),           # 8 mod 16
+]
+_H16_ROWS = (
+    [(e, {}, 0) for e in _H16_ORDER]
+    + [(e, v, -1) for e in _H16_ORDER for v in _H16_COMMON if set(v) <= set(_H16_ORDER[e].split())]
+    # fp32-output entries: 32-channel K steps, ldy >= Co, a residual needs dense rows, y alignment is not checked
+    + [(e, dict(Ci=96, x_half=0), 0) for e in ("bev_conv2d_h16_f32", "bev_conv2d_h16_ex_f32")]
+    + [(e, dict(Ci=48, x_half=0), -1) for e in _H16_F32]
+    + [(e, dict(y=0x30002), 0) for e in _H16_F32]
+    + [(e, dict(ldy=63), -1) for e in ("bev_conv2d_h16_f32", "bev_conv2d_h16_ex_f32")]
+    + [(e, dict(ldy=128), 0) for e in ("bev_conv2d_h16_f32", "bev_conv2d_h16_ex_f32")]
+    + [(e, dict(ldy=128, residual=0x40000), -1) for e in ("bev_conv2d_h16_f32", "bev_conv2d_h16_ex_f32")]
+    + [(e, dict(residual=0x30000), 0) for e in ("bev_conv2d_h16_f32", "bev_conv2d_h16_ex_f32")]  # y may alias it
+    + [("bev_conv2d_h16_bnstats_f32", dict(tile_stats=None), -1),
+       ("bev_conv2d_h16_bnstats_f32", dict(Ci=96), -1),                            # statistics: k_conv_h16b only
+       ("bev_conv2d_h16_ex_f32", dict(tile_stats=0x40000), 0),
+       ("bev_conv2d_h16_ex_f32", dict(tile_stats=0x40000, act=1), -1),
+       ("bev_conv2d_h16_ex_f32", dict(tile_stats=0x40000, residual=0x50000), -1),
+       ("bev_conv2d_h16_ex_f32", dict(tile_stats=0x40000, Ci=96, x_half=0), -1),   # statistics: k_conv_h16b only
+       ("bev_conv2d_h16_ex_f32", dict(x_half=1, Ci=96), -1),                       # fp16 operand: k_conv_h16b only
+       # fp16 in, fp16 out: 64-channel K steps, 8-channel output groups, everything 16-B aligned, no aliasing
+       ("bev_conv2d_h16_h16", dict(x_half=0), 0),
+       ("bev_conv2d_h16_h16", dict(residual=0x40000), 0),
+       ("bev_conv2d_h16_h16", dict(Ci=96), -1),
+       ("bev_conv2d_h16_h16", dict(Co=60), -1),
+       ("bev_conv2d_h16_h16", dict(y=0x30008), -1),
+       ("bev_conv2d_h16_h16", dict(residual=0x40008), -1),
+       ("bev_conv2d_h16_h16", dict(residual=0x30000), -1),                         # y == residual, even with M = 0
+       # operand affine
+       ("bev_conv2d_h16_affine", dict(in_scale=0x50000, in_shift=0x60000, in_relu=1), 0),
+       ("bev_conv2d_h16_affine", dict(x_half=0), 0),
+       ("bev_conv2d_h16_affine", dict(y_half=0, y=0x30004, ldy=128), 0),
+       ("bev_conv2d_h16_affine", dict(y_half=0, Co=60, ldy=60), 0),
+       ("bev_conv2d_h16_affine", dict(ldy=63), -1),
+       ("bev_conv2d_h16_affine", dict(Ci=96), -1),
+       ("bev_conv2d_h16_affine", dict(in_scale=0x50000), -1),
+       ("bev_conv2d_h16_affine", dict(in_shift=0x60000), -1),
+       ("bev_conv2d_h16_affine", dict(in_scale=0x50000, in_shift=0x60000, x_half=0), -1),
+       ("bev_conv2d_h16_affine", dict(Co=60, ldy=60), -1),
+       ("bev_conv2d_h16_affine", dict(ldy=128), -1),
+       ("bev_conv2d_h16_affine", dict(in_scale=0x50008, in_shift=0x60000), -1),
+       ("bev_conv2d_h16_affine", dict(in_scale=0x50000, in_shift=0x60008), -1),
+       ("bev_conv2d_h16_affine", dict(y=0x30008), -1),                             # fp16 y: 16 bytes
+       ("bev_conv2d_h16_affine", dict(y_half=0, y=0x30002), -1)]                   # fp32 y: 4 bytes
+)
+
+
+def _h16_call(lib, entry, changes):
+    args = dict(_H16_BASE, tile_stats=0x40000 if entry == "bev_conv2d_h16_bnstats_f32" else None)
+    args.update(changes)
+    assert args["N"] <= 0, "only empty or rejected calls: nothing may reach a kernel"
+    return getattr(lib, entry)(*[args[k] for k in _H16_ORDER[entry].split()])
+
+
+def test_conv_h16_argument_rules_without_gpu(lib):
+    """The fp16 forward convs' per-entry argument rules: every row is an accepted argument set (-> 0) or that set with
+    one rule broken (-> BEV_ERR_ARGS), with N = 0 so that either answer comes before any HIP call.  No answer depends
+    on BEV_TUNE_CONV_H16_KERNEL: 1 selects the 32-deep kernel for fp32 operands without statistics only, and the
+    fp16-output and affine entries never run it."""
+    import bev_native as nat
+    assert len(_H16_ROWS) > 100 and {e for e, _, _ in _H16_ROWS} == set(_H16_ORDER)
+    bad = [(e, c, want, got) for e, c, want in _H16_ROWS for got in [_h16_call(lib, e, c)] if got != want]
+    assert not bad, bad
+    for kern in (1, 2, 3):
+        with nat.tuned(CONV_H16_KERNEL=kern):
+            bad = [(kern, e, c, want, got) for e, c, want in _H16_ROWS for got in [_h16_call(lib, e, c)] if got != want]
+        assert not bad, bad
+
+
 def test_tune_knobs_host_only(lib):
     """bev_tune: every knob returns its previous value, rejects out-of-range values and unknown knobs;
     no GPU involved (knobs are read at launch)."""

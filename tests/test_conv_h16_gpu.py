@@ -155,11 +155,12 @@ def test_amp_functions_take_half_convs_only_under_autocast():
     dict(N=1, H=40, W=40, Ci=256, Co=64, K=1, stride=1, pad=0, dil=1),
     dict(N=1, H=110, W=110, Ci=256, Co=256, K=3, stride=1, pad=1, dil=1),  # 7 K steps per workgroup in the 64-px kernel
 ], ids=lambda d: f"{d['Ci']}to{d['Co']}k{d['K']}s{d['stride']}d{d['dil']}h{d['H']}")
-@pytest.mark.parametrize("kern", [0, 1], ids=["wgrad64", "wgrad32"])
+@pytest.mark.parametrize("kern", [0, 1], ids=["default", "regtr"])
 def test_wgrad_h16_vs_float64_of_rounded_operands(shape, kern):
     """conv_wgrad_ex under half_convs(): fp16 operands, fp32 sums (split over pixels, float atomics) against the
     float64 weight gradient of the fp16-rounded operands; relative to sum |terms| < 2e-6.  kern: bev_tune
-    CONV_H16_KERNEL 0 = k_wgrad_h16b (64-pixel steps, two in flight), 1 = k_wgrad_h16 (32-pixel steps)."""
+    CONV_H16_KERNEL 0 = k_wgrad_h16c (transposing LDS reads) where Ci, Co % 8 == 0, else k_wgrad_h16b; 1 =
+    k_wgrad_h16b (the transpose in registers, the fallback) always."""
     import bev_native as nat
     N, H, W, Ci, Co, K = shape["N"], shape["H"], shape["W"], shape["Ci"], shape["Co"], shape["K"]
     st, pad, dil = shape["stride"], shape["pad"], shape["dil"]
@@ -184,12 +185,12 @@ def test_wgrad_h16_vs_float64_of_rounded_operands(shape, kern):
 
 
 @pytest.mark.parametrize("shape", [
-    dict(N=2, H=20, W=24, Ci=64, Co=128, K=3, stride=1, pad=1, dil=1),
+    dict(N=2, H=20, W=24, Ci=64, Co=128, K=3, stride=1, pad=1, dil=1, regtr=True),  # regtr: again under CONV_H16_KERNEL 1
     dict(N=1, H=33, W=17, Ci=32, Co=200, K=3, stride=2, pad=1, dil=1),
     dict(N=1, H=24, W=72, Ci=160, Co=512, K=3, stride=1, pad=1, dil=1),   # the head's conv1: taps inside 128-k tiles
     dict(N=1, H=16, W=70, Ci=512, Co=128, K=3, stride=1, pad=2, dil=2),   # head conv2 (dilated)
     dict(N=2, H=16, W=19, Ci=128, Co=36, K=3, stride=1, pad=2, dil=2),    # Co % 8 != 0: the register-transpose kernel
-    dict(N=3, H=9, W=11, Ci=96, Co=8, K=1, stride=1, pad=0, dil=1),
+    dict(N=3, H=9, W=11, Ci=96, Co=8, K=1, stride=1, pad=0, dil=1, regtr=True),
     dict(N=1, H=45, W=60, Ci=256, Co=64, K=1, stride=2, pad=0, dil=1),    # the trunk's strided 1x1 downsample
     dict(N=1, H=110, W=110, Ci=64, Co=64, K=3, stride=1, pad=1, dil=1),   # many 64-pixel steps per workgroup
 ], ids=lambda d: f"{d['Ci']}to{d['Co']}k{d['K']}s{d['stride']}d{d['dil']}h{d['H']}")
@@ -198,7 +199,8 @@ def test_wgrad_h16_fp16_gradient_vs_float64(shape, x_half):
     """conv_wgrad_h16_any with the gradient stored in fp16 (the AMP training step's dgrad / BatchNorm-backward
     outputs) and x in fp16 or fp32: k_wgrad_h16c (natural [pixel][channel] LDS images, transposing
     ds_read_b64_tr_b16 fragment reads) where Ci, Co % 8 == 0, else k_wgrad_h16b; against the float64 weight gradient
-    of the fp16 operands, relative to sum |terms| < 2e-6."""
+    of the fp16 operands, relative to sum |terms| < 2e-6.  The two smallest shapes (2x20x24 64->128 k3, 3x9x11 96->8
+    k1) run a second time under CONV_H16_KERNEL 1, which sends them to k_wgrad_h16b, same bound."""
     import bev_native as nat
     N, H, W, Ci, Co, K = shape["N"], shape["H"], shape["W"], shape["Ci"], shape["Co"], shape["K"]
     st, pad, dil = shape["stride"], shape["pad"], shape["dil"]
@@ -216,6 +218,12 @@ def test_wgrad_h16_fp16_gradient_vs_float64(shape, x_half):
     err = (dw.cpu().double() - ref).abs()
     assert dw.shape == (Co, Ci, K, K)
     assert float((err / (mag + 1e-12)).max()) < 2e-6
+    if shape.get("regtr"):  # the two smallest shapes again on the forced fallback, k_wgrad_h16b<x_half, true>
+        with nat.tuned(CONV_H16_KERNEL=1):
+            dw = nat.conv_wgrad_h16_any(xd, dz.to(DEV), K, K, st, pad, dilation=dil)
+        torch.cuda.synchronize()
+        assert dw.shape == (Co, Ci, K, K)
+        assert float(((dw.cpu().double() - ref).abs() / (mag + 1e-12)).max()) < 2e-6
 
 
 @pytest.mark.parametrize("N,H,W,Ci,K,dil,Co,res", [(2, 19, 70, 64, 3, 1, 128, False), (1, 21, 96, 128, 3, 2, 64, True),

@@ -1,5 +1,5 @@
 # Build a variant of libbev_mi355x.so with extra compile definitions into tools/_ab/ (A/B timing only):
-#   bash tools/build_variant.sh lines0 -DH16B_LINES=0
+#   bash tools/build_variant.sh pipe0 -DWARP_PIPE=0
 set -e
 cd "$(dirname "$0")/../vision-based-spatio-temporal-analysis_amd"
 name=$1; shift

@@ -433,15 +433,24 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _require_gpu(*ts):
+def _out_hw(H, W, KH, KW, stride, pad, dilation=1):  # the expression the C entry points check Ho, Wo against
+    return tuple((n + 2 * pad - dilation * (k - 1) - 1) // stride + 1 for n, k in ((H, KH), (W, KW)))
+
+
+def _require_panel(packed, dtype, who):  # the weight panel: a device tensor of the kernel's type (fp16 / split bf16)
+    if not packed.is_cuda or packed.dtype != dtype:
+        raise HipError(f"{who} needs the {'fp16' if dtype == torch.float16 else 'split-bf16'} weight panel on the device")
+
+
+def _require_gpu(*ts, dtypes=(torch.float32,), what="fp32"):
     for t in ts:
         if t is None:
             continue
         if not t.is_cuda:
             raise HipError("libbev_mi355x kernels need ROCm device tensors (got a CPU tensor); "
                            "this package has no CPU fallback")
-        if t.dtype != torch.float32:
-            raise HipError(f"fp32 tensors expected, got {t.dtype}")
+        if t.dtype not in dtypes:
+            raise HipError(f"{what} tensors expected, got {t.dtype}")
 
 
 # ---------------------------------------------------------------------------
@@ -806,11 +815,10 @@ def conv2d_nhwc_x6(x, packed: torch.Tensor, bias, Co: int, KH: int, KW: int, str
         x = x.contiguous()
         _require_gpu(x)
     _require_gpu(bias, residual)
-    if not packed.is_cuda or packed.dtype != torch.bfloat16:
-        raise HipError("conv2d_nhwc_x6 needs the split-bf16 weight panel on the device")
+    _require_panel(packed, torch.bfloat16, "conv2d_nhwc_x6")
     N, H, W, Ci = x.shape
     dev = x.device
-    Ho, Wo = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad, dilation)
     ys = None
     if split_out:
         assert out is None
@@ -842,7 +850,7 @@ def conv2d_stem_x6(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, Co
     N, Ci, H, W = x.shape
     if Ci != 3 or not packed.is_cuda or packed.dtype != torch.bfloat16:
         raise HipError("conv2d_stem_x6 takes NCHW 3-channel images and the split (bf16) weight panel on the device")
-    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    Ho, Wo = _out_hw(H, W, 7, 7, 2, 3)
     if out is None:
         out = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float32)
     with _span("conv", x):
@@ -860,8 +868,8 @@ def conv2d_stem_pool_x6(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tenso
     N, Ci, H, W = x.shape
     if Ci != 3 or Co != 64 or not packed.is_cuda or packed.dtype != torch.bfloat16:
         raise HipError("conv2d_stem_pool_x6 takes NCHW 3-channel images, Co 64 and the split (bf16) weight panel")
-    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
+    Ho, Wo = _out_hw(H, W, 7, 7, 2, 3)
+    Hp, Wp = _out_hw(Ho, Wo, 3, 3, 2, 1)
     ws_bytes = int(lib().bev_conv2d_stem_pool_x6_workspace(N, H, W))
     _check(min(ws_bytes, 0), "bev_conv2d_stem_pool_x6_workspace")
     ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
@@ -895,7 +903,7 @@ def conv2d_nhwc(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, KH: int, K
         N, Ci, H, W = x.shape
     else:
         N, H, W, Ci = x.shape
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad)
     if out is None:
         out = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float32)
     if residual is not None:
@@ -926,10 +934,9 @@ def conv2d_nhwc_h16_bnstats(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: 
     (sum, sum of squared deviations from the tile mean), channel-major [Co, tiles, 2]) for batchnorm_finalize_tiles."""
     x = x.contiguous()
     _require_gpu(x)
-    if not packed.is_cuda or packed.dtype != torch.float16:
-        raise HipError("conv2d_nhwc_h16_bnstats needs the fp16 weight panel on the device")
+    _require_panel(packed, torch.float16, "conv2d_nhwc_h16_bnstats")
     N, H, W, Ci = x.shape
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad)
     z = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float32)
     nt = lib().bev_conv_h16_stat_tiles(N * Ho * Wo)
     _check(0 if nt > 0 else nt, "bev_conv_h16_stat_tiles")
@@ -944,14 +951,7 @@ def conv2d_nhwc_h16_bnstats(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: 
 # ---- fp16-STORED operands of the autocast convs (bit-identical: the kernels round these operands to fp16 anyway) ----
 def _require_gpu_h(*ts):
     """Like _require_gpu, but fp16 tensors are accepted (operands stored in the precision the kernel computes in)."""
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise HipError("libbev_mi355x kernels need ROCm device tensors (got a CPU tensor); "
-                           "this package has no CPU fallback")
-        if t.dtype not in (torch.float32, torch.float16):
-            raise HipError(f"fp32 / fp16 tensors expected, got {t.dtype}")
+    _require_gpu(*ts, dtypes=(torch.float32, torch.float16), what="fp32 / fp16")
 
 
 def conv2d_h16_any(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: int, KW: int, stride: int, pad: int,
@@ -964,11 +964,9 @@ def conv2d_h16_any(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: int, KW: 
     x = x.contiguous()
     _require_gpu_h(x)
     _require_gpu(residual, bias)
-    if not packed.is_cuda or packed.dtype != torch.float16:
-        raise HipError("conv2d_h16_any needs the fp16 weight panel on the device")
+    _require_panel(packed, torch.float16, "conv2d_h16_any")
     N, H, W, Ci = x.shape
-    Ho = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad, dilation)
     if out is not None:
         assert (out.shape[:3] == (N, Ho, Wo) and out.shape[3] >= Co and out.is_contiguous() and out.is_cuda
                 and out.dtype == torch.float32 and residual is None and not stats)
@@ -1000,11 +998,9 @@ def conv2d_h16_half(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, C
     x = x.contiguous()
     _require_gpu_h(x)
     _require_gpu(bias)
-    if not packed.is_cuda or packed.dtype != torch.float16:
-        raise HipError("conv2d_h16_half needs the fp16 weight panel on the device")
+    _require_panel(packed, torch.float16, "conv2d_h16_half")
     N, H, W, Ci = x.shape
-    Ho = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad, dilation)
     if residual is not None:
         if not residual.is_cuda or residual.dtype != torch.float16 or tuple(residual.shape) != (N, Ho, Wo, Co):
             raise HipError("conv2d_h16_half: the residual is an fp16 NHWC device tensor of the output's shape")
@@ -1036,8 +1032,7 @@ def conv2d_h16_affine(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, K: i
     x = x.contiguous()
     _require_gpu_h(x)
     _require_gpu(bias, in_scale, in_shift)
-    if not packed.is_cuda or packed.dtype != torch.float16:
-        raise HipError("conv2d_h16_affine needs the fp16 weight panel on the device")
+    _require_panel(packed, torch.float16, "conv2d_h16_affine")
     if (in_scale is None) != (in_shift is None):
         raise HipError("conv2d_h16_affine: in_scale and in_shift come together")
     N, H, W, Ci = x.shape
@@ -1047,7 +1042,7 @@ def conv2d_h16_affine(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, K: i
         if tuple(in_scale.shape) != (N, Ci) or tuple(in_shift.shape) != (N, Ci):
             raise HipError("conv2d_h16_affine: in_scale / in_shift are [N, Ci]")
         in_scale, in_shift = in_scale.contiguous(), in_shift.contiguous()
-    Ho, Wo = H + 2 * pad - dilation * (K - 1), W + 2 * pad - dilation * (K - 1)
+    Ho, Wo = _out_hw(H, W, K, K, 1, pad, dilation)
     if out is not None:
         want = torch.float16 if y_half else torch.float32
         if not (out.is_cuda and out.dtype == want and tuple(out.shape[:3]) == (N, Ho, Wo) and out.is_contiguous()
@@ -1220,10 +1215,9 @@ def conv2d_nhwc_h16(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, KH: in
     NHWC `out`)."""
     x = x.contiguous()
     _require_gpu(x, bias, residual)
-    if not packed.is_cuda or packed.dtype != torch.float16:
-        raise HipError("conv2d_nhwc_h16 needs the fp16 weight panel on the device")
+    _require_panel(packed, torch.float16, "conv2d_nhwc_h16")
     N, H, W, Ci = x.shape
-    Ho, Wo = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad, dilation)
     if out is None:
         out = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float32)
     assert out.shape[:3] == (N, Ho, Wo) and out.shape[3] >= Co and out.is_contiguous() and out.dtype == torch.float32
@@ -1244,7 +1238,7 @@ def dwconv2d_nhwc(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, K: int,
     x = x.contiguous()
     _require_gpu(x, wt, bias)
     N, H, W, C = x.shape
-    Ho, Wo = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+    Ho, Wo = _out_hw(H, W, K, K, stride, pad)
     y = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float32)
     psum = None
     if want_psum:
@@ -1287,7 +1281,7 @@ def ir_expand_dw(x: torch.Tensor, we: torch.Tensor, be: torch.Tensor, wd: torch.
     N, H, W, Ci = x.shape
     Cm = we.shape[0]
     pad = K // 2
-    Ho, Wo = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+    Ho, Wo = _out_hw(H, W, K, K, stride, pad)
     nb = lib().bev_ir_expand_dw_blocks(Ho, Wo, K, stride)
     _check(0 if nb > 0 else nb, "bev_ir_expand_dw_blocks")
     y = torch.empty(N, Ho, Wo, Cm, device=x.device, dtype=torch.float32)
@@ -1367,7 +1361,7 @@ def conv2d_chain_nhwc(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, KH: 
     if not (packed.is_cuda and packed2.is_cuda and packed.dtype == packed2.dtype):
         raise HipError("conv2d_chain_nhwc needs both weight panels on the device, in one arithmetic")
     N, H, W, Ci = x.shape
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad)
     if out is None:
         out = torch.empty(N, Ho, Wo, Co2, device=x.device, dtype=torch.float32)
     if residual is not None:
@@ -1409,7 +1403,7 @@ def conv2d_chain_dual_nhwc(x: torch.Tensor, packed: torch.Tensor, bias, Co: int,
         raise HipError("conv2d_chain_dual_nhwc needs both weight panels on the device, in one arithmetic")
     N, H, W, Ci = x.shape
     _, H2, W2, Ci2 = x2.shape
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad)
     if out is None:
         out = torch.empty(N, Ho, Wo, Co2, device=x.device, dtype=torch.float32)
     if packed.dtype == torch.bfloat16:  # split-bf16 arithmetic
@@ -1433,7 +1427,7 @@ def maxpool_nhwc(x: torch.Tensor, k: int, stride: int, pad: int) -> torch.Tensor
     x = x.contiguous()
     _require_gpu(x)
     N, H, W, C = x.shape
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    Ho, Wo = _out_hw(H, W, k, k, stride, pad)
     y = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float32)
     _check(lib().bev_maxpool2d_nhwc_f32(_ptr(x), N, H, W, C, k, stride, pad, _ptr(y), Ho, Wo, _stream(x)),
            "bev_maxpool2d_nhwc_f32")
@@ -1515,7 +1509,7 @@ def maxpool_fwd_arg_nhwc(x: torch.Tensor, k: int, stride: int, pad: int):
     x = x.contiguous()
     _require_gpu(x)
     N, H, W, C = x.shape
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    Ho, Wo = _out_hw(H, W, k, k, stride, pad)
     y = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float32)
     arg = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.uint8)
     _check(lib().bev_maxpool2d_fwd_arg_nhwc_f32(_ptr(x), N, H, W, C, k, stride, pad, _ptr(y), _ptr(arg), Ho, Wo,
@@ -1742,7 +1736,7 @@ def conv2d_nhwc_ex(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, K: int,
         return conv2d_nhwc_h16(x, packed, bias, Co, K, K, 1, pad, dilation, int(relu), out=out)
     _require_gpu(x, packed, bias, in_scale, in_shift)
     N, H, W, Ci = x.shape
-    Ho, Wo = H + 2 * pad - dilation * (K - 1), W + 2 * pad - dilation * (K - 1)
+    Ho, Wo = _out_hw(H, W, K, K, 1, pad, dilation)
     if out is None:
         out = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float32)
     assert out.shape[:3] == (N, Ho, Wo) and out.shape[3] >= Co and out.stride(3) == 1 and out.is_contiguous()

@@ -31,8 +31,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in VGPRs (uint4 arrays went to scratch)
 
 constexpr int HBM = 128, HBN = 128, HBK = 32;
-int g_h16_kernel = 0;  // BEV_TUNE_CONV_H16_KERNEL: 0 = k_conv_h16b where Ci % 64 == 0 and k_wgrad_h16b, 1 = k_conv_h16
-                       // and k_wgrad_h16 always
+int g_h16_kernel = 0;  // BEV_TUNE_CONV_H16_KERNEL: 0 = k_conv_h16b where Ci % 64 == 0 and k_wgrad_h16c where it applies,
+                       // 1 = k_conv_h16 (fp32 operands without statistics) and k_wgrad_h16b always
 int g_h16_buf = 1;     // BEV_TUNE_CONV_H16_BUF: 1 = fp16-stored operands staged by raw buffer loads where they apply,
                        // 0 = the pointer form always (what operands of 2 GiB and more run on)
 constexpr int HROW = 40;  // halves per LDS row: 32 + 8 pad = 80 B = 5 slots (odd: 16 rows -> 16 distinct slots)
@@ -214,15 +214,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16(ConvH a) {
 // and the operands of steps s + 1 and s + 2 are in flight in two register sets while step s runs (ping-pong, two
 // steps per trip, no copies).  Same fragment map, same per-output K order (16-deep slices in increasing k): results
 // identical to k_conv_h16.
-constexpr int HBK2 = 64, HROW2 = 72;
-// H16B_LINES 1: the fp16 operand and the weight panel are staged with eight lanes per 128-B K-step row, so every
-// wave load instruction reads whole lines (round 5); 0: the round-4 maps (4 / 2 lanes per row, 32-64 B pieces).
-#ifndef H16B_LINES
-#define H16B_LINES 1
-#endif
-#ifndef H16B_BUF
-#define H16B_BUF 1
-#endif  // halves per LDS row: 64 + 8 pad = 144 B = 9 odd 16-B slots
+// The fp16 operand and the weight panel are staged with eight lanes per 128-B K-step row, so every wave load
+// instruction reads whole lines; the earlier maps (4 / 2 lanes per row, 32-64 B pieces) were 4-5 % slower on the head
+// convs and are gone, as is the build without buffer loads (profiles/r05p_conv_h16_lines_ab.txt,
+// r05r_wgrad_tr_buf_ab.txt).
+constexpr int HBK2 = 64, HROW2 = 72;  // HROW2: halves per LDS row, 64 + 8 pad = 144 B = 9 odd 16-B slots
 
 // BatchNorm statistics of the conv output z = acc + bias (training forward, BN with batch statistics), fused into
 // the epilogue so z is not read back: per output column of the 128 x 128 tile, over the tile's valid rows,
@@ -303,7 +299,7 @@ __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&ac
 // BN: output columns per workgroup.  128: 2 x 2 waves of 64 x 64 (2 x 2 MFMA tiles each); 64 (outputs of <= 64
 // channels: no zero half of the panel loaded or multiplied): 4 x 1 waves of 32 x 64 (1 x 2 tiles).  Per output the
 // K order is the same, so both give identical conv results.
-// BUF (fp16 operand, H16B_LINES, operand and panel < 2 GiB): the staging loads are raw buffer loads with 32-bit
+// BUF (fp16 operand, operand and panel < 2 GiB): the staging loads are raw buffer loads with 32-bit
 // offsets -- per row a constant base, per K step one uniform tap offset (SGPR), and taps outside the image read
 // through an out-of-range offset, which the buffer returns as zeros; the weight panel's K step is the SGPR soffset.
 // Same values in LDS, so results are identical to the pointer form (r05q counters: ~7 VALU per MFMA there, mostly
@@ -316,7 +312,7 @@ __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&ac
 // of 2 B per lane at a pixel stride.  Same mainloop, same (acc + bias) + residual order as the fp32 epilogue: every
 // output is the fp32-output kernel's value rounded to fp16.  A template parameter, not a runtime branch: the
 // HOUT = false instances are unchanged.
-// AFF (bev_conv2d_h16_affine; fp16 operand, whole-line map): the operand is the previous layer's conv output z stored
+// AFF (bev_conv2d_h16_affine; fp16 operand): the operand is the previous layer's conv output z stored
 // in fp16, and its GroupNorm affine + ReLU is applied between the staging registers and the LDS store,
 //     a = f16_rne( max( float(z) * scale[n][ci] + shift[n][ci], 0 ) )      (one fp32 multiply, one fp32 add)
 // -- k_gn_apply<_Float16>'s expression, so the LDS image is what that kernel would have written and the normalised
@@ -331,7 +327,7 @@ __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&ac
 constexpr int AFF_TC = 512;
 template <bool HIN, int BN, bool BUF = false, bool HOUT = false, bool AFF = false>
 __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
-    static_assert(!AFF || (HIN && H16B_LINES), "operand affine: fp16 operand, whole-line map");
+    static_assert(!AFF || HIN, "operand affine: fp16 operand");
     constexpr int TI = BN == 128 ? 2 : 1, WROWS = BN == 128 ? 64 : 32, NBU = BN == 128 ? 4 : 2;
     __shared__ __attribute__((aligned(16))) _Float16 lds[2][(HBM + BN) * HROW2];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -349,11 +345,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
     const int64_t m0 = mt * HBM;
     const int n0 = nt * BN;
     // A staging.  fp32 operand: rows (tid >> 2) + 64 q (q < 2), channel quads (tid & 3) + 4 u (u < 4), 16-B loads.
-    // fp16 operand (H16B_LINES): rows (tid >> 3) + 32 q (q < 4), halves 8 (tid & 7) .. + 7 -- eight lanes read one
-    // pixel's 128-B K step, so each wave load is 8 whole lines instead of 16 rows x 32 B.
-    constexpr bool LN = HIN && H16B_LINES;
-    constexpr int NQ = LN ? 4 : 2, ARS = LN ? 32 : 64;
-    const int aq = LN ? (tid & 7) : (tid & 3), arow = LN ? (tid >> 3) : (tid >> 2);
+    // fp16 operand: rows (tid >> 3) + 32 q (q < 4), halves 8 (tid & 7) .. + 7 -- eight lanes read one pixel's 128-B
+    // K step, so each wave load is 8 whole lines instead of 16 rows x 32 B.
+    constexpr int NQ = HIN ? 4 : 2, ARS = HIN ? 32 : 64;
+    const int aq = HIN ? (tid & 7) : (tid & 3), arow = HIN ? (tid >> 3) : (tid >> 2);
     int64_t pix[NQ];
     int iy0[NQ], ix0[NQ];
     bool rok[NQ];
@@ -367,7 +362,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
         const int64_t t = mm / a.Wo;
         const int oy = (int)(t % a.Ho);
         const int n = (int)(t / a.Ho);
-        pix[q] = (int64_t)n * a.H * a.W * a.Ci + (LN ? 8 : 4) * aq;
+        pix[q] = (int64_t)n * a.H * a.W * a.Ci + (HIN ? 8 : 4) * aq;
         iy0[q] = oy * a.stride - a.pad;
         ix0[q] = ox * a.stride - a.pad;
         if constexpr (AFF) nimg[q] = n;
@@ -385,15 +380,13 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
             if (c < a.Ci) atv = *(const f32x4 *)((tid < 128 ? a.in_scale : a.in_shift) + (int64_t)ntab * a.Ci + c);
         }
     }
-    // B staging (H16B_LINES): weight rows n0 + (tid >> 3) + 32 u (u < NBU), halves 8 (tid & 7) .. + 7 of the K step
-    // (whole 128-B lines per wave load).  Otherwise row n0 + (tid >> 1), halves 32 (tid & 1) .. + 31 (BN 64: row
-    // n0 + (tid >> 2), halves 16 (tid & 3) .. + 15).
-    const int brow = H16B_LINES ? tid >> 3 : BN == 128 ? tid >> 1 : tid >> 2;
-    const int bcol = H16B_LINES ? 8 * (tid & 7) : BN == 128 ? 32 * (tid & 1) : 16 * (tid & 3);
-    const int64_t bstep = H16B_LINES ? 32 * (int64_t)a.Kp : 8;  // halves between a thread's NBU weight loads
-    const int bls = H16B_LINES ? 32 * HROW2 : 8;                 // ... and between its LDS stores
+    // B staging: weight rows n0 + (tid >> 3) + 32 u (u < NBU), halves 8 (tid & 7) .. + 7 of the K step (whole 128-B
+    // lines per wave load)
+    const int brow = tid >> 3, bcol = 8 * (tid & 7);
+    const int64_t bstep = 32 * (int64_t)a.Kp;  // halves between a thread's NBU weight loads
+    const int bls = 32 * HROW2;                // ... and between its LDS stores
     const _Float16 *wrow = a.wp + (int64_t)(n0 + brow) * a.Kp + bcol;
-    static_assert(!BUF || LN, "buffer staging: fp16 operand, whole-line map");
+    static_assert(!BUF || HIN, "buffer staging: fp16 operand");
     __amdgpu_buffer_rsrc_t rsx, rsw;
     int xrb[NQ], wvo[NBU];  // BUF: byte offsets of row q's (0, 0) tap piece / of weight load u at K step 0
     if constexpr (BUF) {
@@ -412,7 +405,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
     int ky = 0, kx = 0, ci0 = 0;
     int64_t kb = 0;
     f32x4 ra0[8], ra1[8];
-    h16x8 rh0[4], rh1[4];  // LN: one 16-B line piece per row q; else pairs of the old map's 8-B quads
+    h16x8 rh0[4], rh1[4];  // HIN: one 16-B line piece per row q
     u32x4 rb0[NBU], rb1[NBU];
 #define H16_GLOAD(RA, RH, RB, RM, RC)                                                                      \
     do {                                                                                                   \
@@ -430,7 +423,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
                                                       rsx, in ? xrb[q] + toff : (int)0x80000000, 0, 0));   \
                 if constexpr (AFF) RM |= in ? 1 << q : 0;                                                  \
             }                                                                                              \
-        } else if constexpr (LN) {                                                                         \
+        } else if constexpr (HIN) {                                                                        \
             _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                               \
                 const int iy = iy0[q] + dy, ix = ix0[q] + dx;                                              \
                 const bool in = rok[q] && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;    \
@@ -444,19 +437,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
                 const bool in = rok[q] && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;    \
                 const int64_t e = pix[q] + ((int64_t)iy * a.W + ix) * a.Ci + ci0;                          \
                 const int st = in ? 16 : 0; /* the zero quad is re-read for every u */                     \
-                if constexpr (HIN) {                                                                       \
-                    const _Float16 *src = in ? a.xh + e : (const _Float16 *)g_hzero4;                      \
-                    _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                        \
-                        const h16x4 v = *(const h16x4 *)(src + st * u);                                    \
-                        RH[(4 * q + u) >> 1][4 * (u & 1) + 0] = v[0];                                      \
-                        RH[(4 * q + u) >> 1][4 * (u & 1) + 1] = v[1];                                      \
-                        RH[(4 * q + u) >> 1][4 * (u & 1) + 2] = v[2];                                      \
-                        RH[(4 * q + u) >> 1][4 * (u & 1) + 3] = v[3];                                      \
-                    }                                                                                      \
-                } else {                                                                                   \
-                    const float *src = in ? a.x + e : g_hzero4;                                            \
-                    _Pragma("unroll") for (int u = 0; u < 4; ++u) RA[4 * q + u] = *(const f32x4 *)(src + st * u); \
-                }                                                                                          \
+                const float *src = in ? a.x + e : g_hzero4;                                                \
+                _Pragma("unroll") for (int u = 0; u < 4; ++u) RA[4 * q + u] = *(const f32x4 *)(src + st * u); \
             }                                                                                              \
         }                                                                                                  \
         if constexpr (BUF) {                                                                               \
@@ -502,15 +484,12 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
                 }                                                                                          \
                 *(h16x8 *)(As + (arow + 32 * q) * HROW2 + 8 * aq) = v_;                                    \
             }                                                                                              \
-        } else if constexpr (LN) {                                                                         \
+        } else if constexpr (HIN) {                                                                        \
             _Pragma("unroll") for (int q = 0; q < NQ; ++q)                                                 \
                 *(h16x8 *)(As + (arow + 32 * q) * HROW2 + 8 * aq) = RH[q];                                 \
         } else {                                                                                           \
             _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                \
-                h16x4 hv;                                                                                  \
-                if constexpr (HIN) hv = (h16x4){RH[q >> 1][4 * (q & 1)], RH[q >> 1][4 * (q & 1) + 1],      \
-                                                RH[q >> 1][4 * (q & 1) + 2], RH[q >> 1][4 * (q & 1) + 3]}; \
-                else hv = (h16x4){(_Float16)RA[q][0], (_Float16)RA[q][1], (_Float16)RA[q][2], (_Float16)RA[q][3]}; \
+                const h16x4 hv = {(_Float16)RA[q][0], (_Float16)RA[q][1], (_Float16)RA[q][2], (_Float16)RA[q][3]}; \
                 *(h16x4 *)(As + (arow + 64 * (q >> 2)) * HROW2 + 4 * aq + 16 * (q & 3)) = hv;              \
             }                                                                                              \
         }                                                                                                  \
@@ -649,140 +628,20 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
 
 // ---- weight gradient under autocast(float16): dW[co][k] = sum_m f16(dz[m][co]) * f16(im2col(x)[m][k]) ----------
 // The reduction index of v_mfma_f32_32x32x16_f16 is the output pixel m: lane l needs 8 consecutive pixels of one
-// channel (A = dz^T, B = im2col(x)), so both operands are staged TRANSPOSED into LDS as fp16 [channel][pixel]
-// rows of 40 halves (the forward kernel's conflict-free 80-B rows).  Each thread loads four pixel rows of one
-// channel quad (float4, coalesced along channels), rounds them to fp16 and writes each channel's four pixels
-// as one ds_write_b64.  Block tile 128 (co) x 128 (k), 2 x 2 waves of 64 x 64, 32 pixels per step, registers
-// prefetched one step ahead, double-buffered LDS; the pixel range is split over workgroups and the partial
-// tiles are added with float atomics (summation order varies in the last bits, as in the fp32 kernels).
-constexpr int WT = 128, WMS = 32;
+// channel (A = dz^T, B = im2col(x)), so both operands reach the MFMA TRANSPOSED, as fp16 [channel][pixel] fragments.
+// Block tile 128 (co) x 128 (k), 2 x 2 waves of 64 x 64, 64 pixels per step (16 MFMAs per wave and barrier), the
+// loads of steps s + 1 and s + 2 in two register sets while step s runs (as in k_conv_h16b), double-buffered LDS; the
+// pixel range is split over workgroups in chunks that are multiples of 64 and the partial tiles are added with float
+// atomics (summation order varies in the last bits, as in the fp32 kernels).  The first kernel of this kind (32-pixel
+// steps, one step in flight: 51.8 -> 44.5 ms against k_wgrad_h16b) was retired; 4f78a2a is the last tree
+// with it.
+constexpr int WT = 128, WMS2 = 64, WROW2 = 72;
 
-__global__ __launch_bounds__(256, 2) void k_wgrad_h16(const float *__restrict__ x, const float *__restrict__ dz,
-                                                       int N, int H, int W, int Ci, int Ho, int Wo, int Co, int KW,
-                                                       int K, int stride, int pad, int dil, int64_t mchunk, int ctiles,
-                                                       int ntiles, float *__restrict__ dW) {
-    __shared__ __attribute__((aligned(16))) _Float16 lds[2][2 * WT * HROW];
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
-    const int tile = (int)(bid % (unsigned)ntiles);
-    const int64_t split = bid / (unsigned)ntiles;
-    const int co0 = (tile % ctiles) * WT, k0 = (tile / ctiles) * WT;
-    const int64_t M = (int64_t)N * Ho * Wo;
-    const int64_t mb = split * mchunk, me = mb + mchunk < M ? mb + mchunk : M;
-    if (mb >= me) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const int rg = tid >> 5, q = tid & 31;  // staging: pixel rows 4 rg .. 4 rg + 3, channel quad q
-    const int co = co0 + 4 * q;
-    const bool co_ok = co < Co;
-    const int k = k0 + 4 * q;  // 4 consecutive k inside one tap (Ci % 4 == 0)
-    const bool k_ok = k < K;
-    const int tap = k_ok ? k / Ci : 0, ci = k - tap * Ci, ky = tap / KW, kx = tap - ky * KW;
-    // (image, row, column) of this thread's first pixel row in the current step
-    int px, py, pn;
-    {
-        const int64_t m = mb + 4 * rg, t = m / Wo;
-        px = (int)(m - t * Wo);
-        py = (int)(t % Ho);
-        pn = (int)(t / Ho);
-    }
-    int64_t ms = mb;
-    f32x4 ra[4], rb[4];
-    auto gload = [&]() {
-        int x1 = px, y1 = py, n1 = pn;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t m = ms + 4 * rg + r;
-            const bool mok = m < me;
-            ra[r] = (mok && co_ok) ? *(const f32x4 *)(dz + m * Co + co) : (f32x4){0.f, 0.f, 0.f, 0.f};
-            const int iy = y1 * stride - pad + ky * dil, ix = x1 * stride - pad + kx * dil;
-            const bool in = mok && k_ok && iy >= 0 && iy < H && ix >= 0 && ix < W;
-            rb[r] = in ? *(const f32x4 *)(x + (((int64_t)n1 * H + iy) * W + ix) * Ci + ci) : (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (++x1 == Wo) {
-                x1 = 0;
-                if (++y1 == Ho) {
-                    y1 = 0;
-                    ++n1;
-                }
-            }
-        }
-        ms += WMS;
-        px += WMS;
-        while (px >= Wo) {
-            px -= Wo;
-            if (++py == Ho) {
-                py = 0;
-                ++pn;
-            }
-        }
-    };
-    auto swrite = [&](int buf) {
-        _Float16 *As = lds[buf], *Bs = As + WT * HROW;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const h16x4 ha = {(_Float16)ra[0][c], (_Float16)ra[1][c], (_Float16)ra[2][c], (_Float16)ra[3][c]};
-            const h16x4 hb = {(_Float16)rb[0][c], (_Float16)rb[1][c], (_Float16)rb[2][c], (_Float16)rb[3][c]};
-            *(h16x4 *)(As + (4 * q + c) * HROW + 4 * rg) = ha;
-            *(h16x4 *)(Bs + (4 * q + c) * HROW + 4 * rg) = hb;
-        }
-    };
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x16){0};
-    const int nsteps = (int)((me - mb + WMS - 1) / WMS);
-    gload();
-    swrite(0);
-    __syncthreads();
-    const int r32 = lane & 31, h = lane >> 5;
-    for (int st = 0; st < nsteps; ++st) {
-        const bool more = st + 1 < nsteps;
-        if (more) gload();
-        const _Float16 *As = lds[st & 1], *Bs = As + WT * HROW;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            h16x8 fa[2], fb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = *(const h16x8 *)(As + (wm * 64 + i * 32 + r32) * HROW + kk * 16 + 8 * h);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fb[j] = *(const h16x8 *)(Bs + (wn * 64 + j * 32 + r32) * HROW + kk * 16 + 8 * h);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) swrite((st + 1) & 1);
-        __syncthreads();
-    }
-    // D[row][col]: row = co (A rows), col = k; row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), col = lane & 31
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kc = k0 + wn * 64 + j * 32 + r32;
-            if (kc >= K) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cr = co0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (cr < Co) atomicAdd(dW + (int64_t)cr * K + kc, acc[i][j][r]);
-            }
-        }
-}
-
-// ---- k_wgrad_h16b: 64 pixels per K step, two steps of operands in flight -----------------------------------------
-// k_wgrad_h16's 32-pixel step gives a wave 8 MFMAs (~256 cycles) per barrier with one step of loads in flight: the
-// global-load latency is exposed (the weight gradient was 15 % of the AMP training step).  Here a step is 64 pixels
-// (16 MFMAs per wave) and, as in k_conv_h16b, the loads of steps s + 1 and s + 2 sit in two register sets while
-// step s runs.  Staging: thread (rg = tid >> 5, q = tid & 31) loads pixel rows 8 rg .. 8 rg + 7 of channel quad q
-// of both operands and writes each channel's 8 pixels as ONE ds_write_b128 ([channel][pixel] rows of 72 halves:
-// 9 odd 16-B slots, conflict-free fragment reads).  Same per-element products; pixel chunks per workgroup are
-// multiples of 64 (fp32-tolerance equal to k_wgrad_h16, float atomics across chunks as there).
+// ---- k_wgrad_h16b: the transpose in registers (the fallback: any Ci, Co % 4 == 0, 8-B aligned, 64-bit offsets) -----
+// Staging: thread (rg = tid >> 5, q = tid & 31) loads pixel rows 8 rg .. 8 rg + 7 of channel quad q of both operands
+// (float4 or 4 halves, coalesced along channels) and writes each channel's 8 pixels as ONE ds_write_b128 ([channel]
+// [pixel] rows of 72 halves: 9 odd 16-B slots, conflict-free fragment reads).
 // XH / DH: x / dz arrive in fp16 (the values the fp32 path rounds them to: bit-identical products).
-constexpr int WMS2 = 64, WROW2 = 72;
 
 template <bool XH, bool DH>
 __global__ __launch_bounds__(256, 2) void k_wgrad_h16b(const float *__restrict__ x, const float *__restrict__ dz,
@@ -929,6 +788,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_h16b(const float *__restrict__
 #undef WG16_MFMA
 #undef WG16_STORE
 #undef WG16_LOAD
+    // D[row][col]: row = co (A rows), col = k; row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), col = lane & 31
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -953,9 +813,8 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_h16b(const float *__restrict__
 // every workgroup's partial tile is bit-identical to it; only the float-atomic order across chunks varies (as
 // there).  dz (DH) and x (XH) in fp16, or fp32 rounded to fp16 in the staging write (as k_wgrad_h16b does).
 // Requires Ci % 8 == 0 and Co % 8 == 0 (a 16-B piece inside one tap / one output row) and 16-B aligned operands.
-#ifndef H16_WGRAD_TR
-#define H16_WGRAD_TR 1
-#endif
+// 1.4-1.7x k_wgrad_h16b on the trunk's layers (profiles/r05r_wgrad_tr_buf_ab.txt); BEV_TUNE_CONV_H16_KERNEL 1 runs
+// k_wgrad_h16b in its place.
 typedef short s16x4v __attribute__((vector_size(8)));
 
 __device__ __forceinline__ h16x4 lds_tr16(const _Float16 *p) {
@@ -1140,6 +999,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_h16c(const float *__restrict__
 #undef WG16C_FRAG
 #undef WG16C_STORE
 #undef WG16C_LOAD
+    // D[row][col]: row = co (A rows), col = k; row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), col = lane & 31
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1154,12 +1014,85 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_h16c(const float *__restrict__
         }
 }
 
-// bev_conv2d_h16_affine's instance: operand affine (fp16 operand), plain fp16 operand, or fp32 operand
-template <int BN, bool BUF, bool HOUT>
-void (*conv_h16_affine_kernel(bool aff, bool x_half))(ConvH) {
-    if (aff) return k_conv_h16b<true, BN, BUF, HOUT, true>;
-    if (x_half) return k_conv_h16b<true, BN, BUF, HOUT>;
-    return k_conv_h16b<false, BN, false, HOUT>;
+// ---- the forward convs' one host path -------------------------------------------------------------------------------
+// What the five entry points differ in (the conv geometry travels beside it).
+struct ConvIo {
+    const void *x;  // operand: fp32, or fp16 with x_half (k_conv_h16b only)
+    int x_half;
+    void *y;  // output: fp32 rows of ldy >= Co words, or with y_half dense fp16 [M][Co] (Co % 8 == 0, 16-B aligned)
+    int y_half, ldy;
+    const void *res;                    // residual [M][Co] of y's type (fp16: not overlapping y), or null
+    float *stats;                       // BatchNorm tile partials of the raw fp32 output, or null
+    const float *in_scale, *in_shift;   // operand affine [N][Ci] (fp16 operand), both or neither
+    int in_relu;
+    bool deep32;  // the entry may run the 32-deep k_conv_h16: Ci % 32 == 0 is enough, CONV_H16_KERNEL 1 selects it
+};
+
+// The 20 k_conv_h16b instances: an fp32 operand has neither buffer staging nor an operand affine.
+template <bool HIN, bool BUF, bool AFF>
+void (*conv_h16b_tile(bool n64, bool hout))(ConvH) {
+    if (n64) return hout ? k_conv_h16b<HIN, 64, BUF, true, AFF> : k_conv_h16b<HIN, 64, BUF, false, AFF>;
+    return hout ? k_conv_h16b<HIN, 128, BUF, true, AFF> : k_conv_h16b<HIN, 128, BUF, false, AFF>;
+}
+void (*conv_h16b_kernel(bool hin, bool n64, bool buf, bool hout, bool aff))(ConvH) {
+    if (!hin) return conv_h16b_tile<false, false, false>(n64, hout);
+    if (aff) return buf ? conv_h16b_tile<true, true, true>(n64, hout) : conv_h16b_tile<true, false, true>(n64, hout);
+    return buf ? conv_h16b_tile<true, true, false>(n64, hout) : conv_h16b_tile<true, false, false>(n64, hout);
+}
+
+int conv_h16(const ConvIo &io, int N, int H, int W, int Ci, const uint16_t *packed, const float *bias, int Co, int KH,
+             int KW, int stride, int pad, int dilation, int act, int Ho, int Wo, void *stream) {
+    if (!io.x || !packed || !io.y || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 || KW <= 0 ||
+        stride <= 0 || pad < 0 || dilation <= 0 || act < 0 || act > 2 || io.ldy < Co)
+        return BEV_ERR_ARGS;
+    if (Ci % (io.deep32 ? HBK : HBK2) != 0) return BEV_ERR_ARGS;  // one tap and 32 / 64 channels per K step
+    if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 ||
+        Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1 || Ho <= 0 || Wo <= 0)
+        return BEV_ERR_ARGS;
+    const bool aff = io.in_scale != nullptr;
+    if ((io.in_shift != nullptr) != aff) return BEV_ERR_ARGS;
+    if (aff && !io.x_half) return BEV_ERR_ARGS;  // the affine is applied to the fp16 staging registers
+    if ((((uintptr_t)io.x | (uintptr_t)packed | (uintptr_t)io.in_scale | (uintptr_t)io.in_shift) & 15) != 0)
+        return BEV_ERR_ARGS;
+    if (io.res && io.ldy != Co) return BEV_ERR_ARGS;
+    const int64_t M = (int64_t)N * Ho * Wo;
+    if (io.y_half) {  // dense fp16 rows, 16-B groups of 8 channels
+        if (Co % 8 != 0 || io.ldy != Co || (((uintptr_t)io.y | (uintptr_t)io.res) & 15) != 0) return BEV_ERR_ARGS;
+        if (io.res) {  // the epilogue reads the residual of a pixel other lanes may already have written: no aliasing
+            const uintptr_t yb = (uintptr_t)io.y, rb = (uintptr_t)io.res, bytes = (uintptr_t)M * Co * 2;
+            if (yb == rb || (yb < rb + bytes && rb < yb + bytes)) return BEV_ERR_ARGS;
+        }
+    }
+    // CONV_H16_KERNEL 1 (the 32-deep kernel, A/B) applies only where that kernel can run: epilogue statistics, fp16
+    // operands and fp16 outputs exist on k_conv_h16b alone, so those calls keep it (as the weight gradient does)
+    const bool wide = Ci % HBK2 == 0 && (!io.deep32 || g_h16_kernel != 1 || io.stats != nullptr || io.x_half);
+    if (io.stats && (!wide || act != 0 || io.res)) return BEV_ERR_ARGS;  // statistics of the raw conv output
+    if (io.x_half && !wide) return BEV_ERR_ARGS;
+    if (N == 0) return 0;
+    ConvH a;
+    a.x = io.x_half ? nullptr : (const float *)io.x;
+    a.xh = io.x_half ? (const _Float16 *)io.x : nullptr;
+    a.wp = (const _Float16 *)packed;
+    a.bias = bias;
+    a.res = (const float *)io.res;  // fp16 [M][Co] in the HOUT instances
+    a.y = (float *)io.y;            // ... and fp16 [M][Co]
+    a.stats = io.stats;
+    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
+    a.dil = dilation, a.Ho = Ho, a.Wo = Wo, a.act = act, a.ldy = io.ldy;
+    a.Kp = (int)kpad_h(Ci * KH * KW);
+    a.M = M;
+    a.in_scale = io.in_scale, a.in_shift = io.in_shift, a.in_relu = io.in_relu;
+    // 64-column tiles for Co <= 64 (2: the 128-column tile always; 3: 64-column tiles always -- A/B, same results)
+    const bool n64 = wide && ((Co <= 64 && g_h16_kernel != 2) || g_h16_kernel == 3);
+    const int64_t blocks = ((M + HBM - 1) / HBM) * (n64 ? (Co + 63) / 64 : (Co + HBN - 1) / HBN);
+    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
+    // buffer staging has 32-bit offsets: operand and panel below 2 GiB (every in-image byte offset, and the
+    // out-of-range sentinel 2^31 above them all)
+    const bool buf = g_h16_buf && io.x_half && (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
+                     copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
+    void (*kern)(ConvH) = wide ? conv_h16b_kernel(io.x_half, n64, buf, io.y_half, aff) : k_conv_h16;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -1199,34 +1132,28 @@ int bev_conv_wgrad_h16_ex_f32(const void *xv, int x_half, int N, int H, int W, i
     if (hipMemsetAsync(dW, 0, (size_t)Co * K * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
     if (M == 0) return 0;
     const int ct = (Co + WT - 1) / WT, kt = (K + WT - 1) / WT, nt = ct * kt;
-    const bool deep = g_h16_kernel != 1 || x_half || dz_half;  // k_wgrad_h16b (64-pixel steps, two in flight); 1:
-                                                               // k_wgrad_h16 (fp32 operands only)
-    const int step = deep ? WMS2 : WMS;
     int64_t sp = 1024 / nt + 1;  // >= ~1024 workgroups
     int64_t mc = (M + sp - 1) / sp;
-    mc = ((mc + step - 1) / step) * step;
+    mc = ((mc + WMS2 - 1) / WMS2) * WMS2;
     sp = (M + mc - 1) / mc;
     if (sp * nt >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
-    const bool tr = H16_WGRAD_TR && deep && Ci % 8 == 0 && Co % 8 == 0 &&
+    // k_wgrad_h16c: 16-B pieces, 32-bit offsets (CONV_H16_KERNEL 1: the register-transpose kernel always, A/B)
+    const bool tr = g_h16_kernel != 1 && Ci % 8 == 0 && Co % 8 == 0 &&
                     (((uintptr_t)x | (uintptr_t)dz) & 15) == 0 && M * Co < ((int64_t)1 << 31) - WMS2 * Co &&
-                    (int64_t)N * H * W * Ci < ((int64_t)1 << 31);  // k_wgrad_h16c: 32-bit offsets
+                    (int64_t)N * H * W * Ci < ((int64_t)1 << 31);
     if (tr) {
         auto kern = x_half ? (dz_half ? k_wgrad_h16c<true, true> : k_wgrad_h16c<true, false>)
                            : (dz_half ? k_wgrad_h16c<false, true> : k_wgrad_h16c<false, false>);
         hipLaunchKernelGGL(kern, dim3((unsigned)(sp * nt)), dim3(256), 0, st, x, (const void *)dz, N, H, W, Ci,
                            Ho, Wo, Co, KW, K, stride, pad, dilation, mc, ct, nt, dW);
-    } else if (deep) {
+    } else {
         auto kern = x_half ? (dz_half ? k_wgrad_h16b<true, true> : k_wgrad_h16b<true, false>)
                            : (dz_half ? k_wgrad_h16b<false, true> : k_wgrad_h16b<false, false>);
         hipLaunchKernelGGL(kern, dim3((unsigned)(sp * nt)), dim3(256), 0, st, x, dz, N, H, W, Ci, Ho, Wo, Co, KW, K,
                            stride, pad, dilation, mc, ct, nt, dW);
     }
-    else
-        hipLaunchKernelGGL(k_wgrad_h16, dim3((unsigned)(sp * nt)), dim3(256), 0, st, x, dz, N, H, W, Ci, Ho, Wo, Co, KW,
-                           K, stride, pad, dilation, mc, ct, nt, dW);
     return (int)hipGetLastError();
 }
-
 
 int bev_conv_wgrad_h16_f32(const float *x, int N, int H, int W, int Ci, const float *dz, int Ho, int Wo, int Co,
                            int KH, int KW, int stride, int pad, int dilation, float *dW, void *stream) {
@@ -1246,164 +1173,18 @@ int bev_conv_pack_weights_h16(const float *w, int Co, int Ci, int KH, int KW, ui
     return (int)hipGetLastError();
 }
 
-static int conv_h16(const void *xv, int x_half, int N, int H, int W, int Ci, const uint16_t *packed, const float *bias,
-                    const float *residual, int Co, int KH, int KW, int stride, int pad, int dilation, int act, float *y,
-                    int ldy, int Ho, int Wo, float *stats, void *stream) {
-    const float *x = (const float *)xv;
-    if (!x || !packed || !y || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 || KW <= 0 ||
-        stride <= 0 || pad < 0 || dilation <= 0 || act < 0 || act > 2 || ldy < Co)
-        return BEV_ERR_ARGS;
-    if (Ci % HBK != 0) return BEV_ERR_ARGS;  // one tap and 32 channels per K step
-    if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 ||
-        Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1 || Ho <= 0 || Wo <= 0)
-        return BEV_ERR_ARGS;
-    if ((((uintptr_t)x | (uintptr_t)packed) & 15) != 0) return BEV_ERR_ARGS;
-    if (residual && ldy != Co) return BEV_ERR_ARGS;
-    // CONV_H16_KERNEL 1 (the 32-deep kernel, A/B) applies only where that kernel can run: epilogue statistics
-    // and fp16-stored operands exist on k_conv_h16b alone, so those calls keep it (as the weight gradient does)
-    const bool wide = Ci % HBK2 == 0 && (g_h16_kernel != 1 || stats != nullptr || x_half);
-    if (stats && (!wide || act != 0 || residual)) return BEV_ERR_ARGS;  // statistics of the raw conv output, k_conv_h16b
-    if (x_half && !wide) return BEV_ERR_ARGS;                         // fp16 operands: k_conv_h16b only
-    if (x_half && ((uintptr_t)x & 7) != 0) return BEV_ERR_ARGS;
-    if (N == 0) return 0;
-    ConvH a;
-    a.x = x_half ? nullptr : x;
-    a.xh = x_half ? (const _Float16 *)xv : nullptr;
-    a.wp = (const _Float16 *)packed;
-    a.bias = bias;
-    a.res = residual;
-    a.y = y;
-    a.stats = stats;
-    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
-    a.dil = dilation, a.Ho = Ho, a.Wo = Wo, a.act = act, a.ldy = ldy;
-    a.Kp = (int)kpad_h(Ci * KH * KW);
-    a.M = (int64_t)N * Ho * Wo;
-    // 64-column tiles for Co <= 64 (2: the 128-column tile always; 3: 64-column tiles always -- A/B, same results)
-    const bool n64 = wide && ((Co <= 64 && g_h16_kernel != 2) || g_h16_kernel == 3);
-    const int64_t blocks = ((a.M + HBM - 1) / HBM) * (n64 ? (Co + 63) / 64 : (Co + HBN - 1) / HBN);
-    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
-    const dim3 g((unsigned)blocks), b(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (wide) {
-        // 32-bit buffer offsets: operand and panel below 2 GiB (every in-image byte offset, and the out-of-range
-        // sentinel 2^31 above them all)
-        const bool buf = H16B_BUF && H16B_LINES && g_h16_buf && x_half &&
-                         (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
-                         copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
-        void (*kern)(ConvH) = n64 ? (x_half ? (buf ? k_conv_h16b<true, 64, true> : k_conv_h16b<true, 64>)
-                                            : k_conv_h16b<false, 64>)
-                                  : (x_half ? (buf ? k_conv_h16b<true, 128, true> : k_conv_h16b<true, 128>)
-                                            : k_conv_h16b<false, 128>);
-        hipLaunchKernelGGL(kern, g, b, 0, st, a);
-    }
-    else
-        hipLaunchKernelGGL(k_conv_h16, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-int bev_conv2d_h16_h16(const void *xv, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
-                       const float *bias, const uint16_t *residual, int Co, int KH, int KW, int stride, int pad,
-                       int dilation, int act, uint16_t *y, int Ho, int Wo, void *stream) {
-    if (!xv || !packed || !y || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
-        pad < 0 || dilation <= 0 || act < 0 || act > 2)
-        return BEV_ERR_ARGS;
-    if (Ci % HBK2 != 0 || Co % 8 != 0) return BEV_ERR_ARGS;  // k_conv_h16b's K step; 16-B groups of 8 output channels
-    if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 ||
-        Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1 || Ho <= 0 || Wo <= 0)
-        return BEV_ERR_ARGS;
-    if ((((uintptr_t)xv | (uintptr_t)packed | (uintptr_t)y | (uintptr_t)residual) & 15) != 0) return BEV_ERR_ARGS;
-    ConvH a;
-    a.M = (int64_t)N * Ho * Wo;
-    if (residual) {  // the epilogue reads the residual of a pixel other lanes may already have written: no aliasing
-        const uintptr_t yb = (uintptr_t)y, rb = (uintptr_t)residual, bytes = (uintptr_t)a.M * Co * 2;
-        if (yb == rb || (yb < rb + bytes && rb < yb + bytes)) return BEV_ERR_ARGS;
-    }
-    if (N == 0) return 0;
-    a.x = x_half ? nullptr : (const float *)xv;
-    a.xh = x_half ? (const _Float16 *)xv : nullptr;
-    a.wp = (const _Float16 *)packed;
-    a.bias = bias;
-    a.res = reinterpret_cast<const float *>(residual);  // fp16 [M][Co] in the HOUT instances
-    a.y = reinterpret_cast<float *>(y);                 // ... and fp16 [M][Co]
-    a.stats = nullptr;
-    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
-    a.dil = dilation, a.Ho = Ho, a.Wo = Wo, a.act = act, a.ldy = Co;
-    a.Kp = (int)kpad_h(Ci * KH * KW);
-    // tile widths as in conv_h16 (CONV_H16_KERNEL 2 / 3 force one; 1 has no fp16-output form and runs as 0)
-    const bool n64 = (Co <= 64 && g_h16_kernel != 2) || g_h16_kernel == 3;
-    const int64_t blocks = ((a.M + HBM - 1) / HBM) * (n64 ? (Co + 63) / 64 : (Co + HBN - 1) / HBN);
-    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
-    const bool buf = H16B_BUF && H16B_LINES && g_h16_buf && x_half &&
-                     (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
-                     copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
-    void (*kern)(ConvH) =
-        n64 ? (x_half ? (buf ? k_conv_h16b<true, 64, true, true> : k_conv_h16b<true, 64, false, true>)
-                      : k_conv_h16b<false, 64, false, true>)
-            : (x_half ? (buf ? k_conv_h16b<true, 128, true, true> : k_conv_h16b<true, 128, false, true>)
-                      : k_conv_h16b<false, 128, false, true>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-int bev_conv2d_h16_affine(const void *xv, int x_half, int N, int H, int W, int Ci, const float *in_scale,
-                          const float *in_shift, int in_relu, const uint16_t *packed, const float *bias, int Co, int KH,
-                          int KW, int stride, int pad, int dilation, int act, void *y, int y_half, int ldy, int Ho,
-                          int Wo, void *stream) {
-    if (!xv || !packed || !y || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
-        pad < 0 || dilation <= 0 || act < 0 || act > 2 || ldy < Co)
-        return BEV_ERR_ARGS;
-    if (Ci % HBK2 != 0) return BEV_ERR_ARGS;  // k_conv_h16b's K step
-    const bool aff = in_scale != nullptr;
-    if ((in_scale == nullptr) != (in_shift == nullptr)) return BEV_ERR_ARGS;
-    if (aff && !x_half) return BEV_ERR_ARGS;  // the affine is applied to the fp16 staging registers
-    if (y_half && (Co % 8 != 0 || ldy != Co)) return BEV_ERR_ARGS;  // dense fp16 rows, 16-B groups of 8 channels
-    if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 ||
-        Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1 || Ho <= 0 || Wo <= 0)
-        return BEV_ERR_ARGS;
-    if ((((uintptr_t)xv | (uintptr_t)packed | (uintptr_t)in_scale | (uintptr_t)in_shift) & 15) != 0)
-        return BEV_ERR_ARGS;
-    if (((uintptr_t)y & (y_half ? 15 : 3)) != 0) return BEV_ERR_ARGS;
-    if (N == 0) return 0;
-    ConvH a;
-    a.x = x_half ? nullptr : (const float *)xv;
-    a.xh = x_half ? (const _Float16 *)xv : nullptr;
-    a.wp = (const _Float16 *)packed;
-    a.bias = bias;
-    a.res = nullptr;
-    a.y = reinterpret_cast<float *>(y);  // fp16 [M][Co] in the HOUT instances
-    a.stats = nullptr;
-    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
-    a.dil = dilation, a.Ho = Ho, a.Wo = Wo, a.act = act, a.ldy = ldy;
-    a.Kp = (int)kpad_h(Ci * KH * KW);
-    a.M = (int64_t)N * Ho * Wo;
-    a.in_scale = in_scale, a.in_shift = in_shift, a.in_relu = in_relu;
-    // tile widths as in conv_h16 (CONV_H16_KERNEL 2 / 3 force one; 1 has no form of this kernel and runs as 0)
-    const bool n64 = (Co <= 64 && g_h16_kernel != 2) || g_h16_kernel == 3;
-    const int64_t blocks = ((a.M + HBM - 1) / HBM) * (n64 ? (Co + 63) / 64 : (Co + HBN - 1) / HBN);
-    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
-    const bool buf = H16B_BUF && H16B_LINES && g_h16_buf && x_half &&
-                     (int64_t)N * H * W * Ci * 2 < ((int64_t)1 << 31) - 16 &&
-                     copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
-    void (*kern)(ConvH);
-    if (n64)
-        kern = y_half ? (buf ? conv_h16_affine_kernel<64, true, true>(aff, x_half)
-                             : conv_h16_affine_kernel<64, false, true>(aff, x_half))
-                      : (buf ? conv_h16_affine_kernel<64, true, false>(aff, x_half)
-                             : conv_h16_affine_kernel<64, false, false>(aff, x_half));
-    else
-        kern = y_half ? (buf ? conv_h16_affine_kernel<128, true, true>(aff, x_half)
-                             : conv_h16_affine_kernel<128, false, true>(aff, x_half))
-                      : (buf ? conv_h16_affine_kernel<128, true, false>(aff, x_half)
-                             : conv_h16_affine_kernel<128, false, false>(aff, x_half));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+int bev_conv2d_h16_ex_f32(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
+                          const float *bias, const float *residual, int Co, int KH, int KW, int stride, int pad,
+                          int dilation, int act, float *y, int ldy, int Ho, int Wo, float *tile_stats, void *stream) {
+    const ConvIo io = {x, x_half, y, 0, ldy, residual, tile_stats, nullptr, nullptr, 0, true};
+    return conv_h16(io, N, H, W, Ci, packed, bias, Co, KH, KW, stride, pad, dilation, act, Ho, Wo, stream);
 }
 
 int bev_conv2d_h16_f32(const float *x, int N, int H, int W, int Ci, const uint16_t *packed, const float *bias,
                        const float *residual, int Co, int KH, int KW, int stride, int pad, int dilation, int act,
                        float *y, int ldy, int Ho, int Wo, void *stream) {
-    return conv_h16(x, 0, N, H, W, Ci, packed, bias, residual, Co, KH, KW, stride, pad, dilation, act, y, ldy, Ho, Wo,
-                    nullptr, stream);
+    return bev_conv2d_h16_ex_f32(x, 0, N, H, W, Ci, packed, bias, residual, Co, KH, KW, stride, pad, dilation, act, y,
+                                 ldy, Ho, Wo, nullptr, stream);
 }
 
 int64_t bev_conv_h16_stat_tiles(int64_t M) { return M > 0 ? (M + HBM - 1) / HBM : BEV_ERR_ARGS; }
@@ -1412,15 +1193,25 @@ int bev_conv2d_h16_bnstats_f32(const float *x, int N, int H, int W, int Ci, cons
                                int Co, int KH, int KW, int stride, int pad, int dilation, float *y, int Ho, int Wo,
                                float *tile_stats, void *stream) {
     if (!tile_stats) return BEV_ERR_ARGS;
-    return conv_h16(x, 0, N, H, W, Ci, packed, bias, nullptr, Co, KH, KW, stride, pad, dilation, 0, y, Co, Ho, Wo,
-                    tile_stats, stream);
+    return bev_conv2d_h16_ex_f32(x, 0, N, H, W, Ci, packed, bias, nullptr, Co, KH, KW, stride, pad, dilation, 0, y, Co,
+                                 Ho, Wo, tile_stats, stream);
 }
 
-int bev_conv2d_h16_ex_f32(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
-                          const float *bias, const float *residual, int Co, int KH, int KW, int stride, int pad,
-                          int dilation, int act, float *y, int ldy, int Ho, int Wo, float *tile_stats, void *stream) {
-    return conv_h16(x, x_half, N, H, W, Ci, packed, bias, residual, Co, KH, KW, stride, pad, dilation, act, y, ldy, Ho,
-                    Wo, tile_stats, stream);
+// The entries below never run k_conv_h16 (it has neither form): CONV_H16_KERNEL 1 runs as 0 there.
+int bev_conv2d_h16_h16(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
+                       const float *bias, const uint16_t *residual, int Co, int KH, int KW, int stride, int pad,
+                       int dilation, int act, uint16_t *y, int Ho, int Wo, void *stream) {
+    const ConvIo io = {x, x_half, y, 1, Co, residual, nullptr, nullptr, nullptr, 0, false};
+    return conv_h16(io, N, H, W, Ci, packed, bias, Co, KH, KW, stride, pad, dilation, act, Ho, Wo, stream);
+}
+
+int bev_conv2d_h16_affine(const void *x, int x_half, int N, int H, int W, int Ci, const float *in_scale,
+                          const float *in_shift, int in_relu, const uint16_t *packed, const float *bias, int Co, int KH,
+                          int KW, int stride, int pad, int dilation, int act, void *y, int y_half, int ldy, int Ho,
+                          int Wo, void *stream) {
+    if (!y_half && ((uintptr_t)y & 3) != 0) return BEV_ERR_ARGS;
+    const ConvIo io = {x, x_half, y, y_half, ldy, nullptr, nullptr, in_scale, in_shift, in_relu, false};
+    return conv_h16(io, N, H, W, Ci, packed, bias, Co, KH, KW, stride, pad, dilation, act, Ho, Wo, stream);
 }
 
 }  // extern "C"

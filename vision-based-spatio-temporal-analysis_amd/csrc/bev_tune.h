@@ -17,7 +17,8 @@ int train_tune(int knob, int value);
 // BEV_TUNE_CONV_X6_TILE / BEV_TUNE_CONV_X6_KERNEL (bev_conv_x6.hip).
 int conv_x6_tune(int knob, int value);
 
-// BEV_TUNE_CONV_H16_KERNEL (bev_conv_h16.hip).
+// BEV_TUNE_CONV_H16_KERNEL (bev_conv_h16.hip): forward tile width / the 32-deep k_conv_h16 (1); weight gradient: 1 =
+// k_wgrad_h16b always, else k_wgrad_h16c where it applies.
 int conv_h16_tune(int value);
 // BEV_TUNE_CONV_H16_BUF (bev_conv_h16.hip).
 int conv_h16_buf_tune(int value);
