@@ -377,6 +377,42 @@ int bev_ir_expand_dw_f32(const float *x, int N, int H, int W, int Ci, const floa
 int bev_conv2d_stem3_f32(const float *x, int N, int H, int W, const float *wt, const float *bias, int Co, int act,
                          float *y, int Ho, int Wo, void *stream);
 
+/* ---- the EfficientNet trunk in the "f16" inference arithmetic (eval, features_only index <= 2) --------------------
+ * Activations NHWC fp16 from the stem to the trunk output; the BN-folded weights rounded once to fp16 (biases and
+ * the SE weights fp32); fp32 accumulation; every stored value rounded once (RNE).  fp16 tensors are passed as
+ * void *.  All pointers 16-B aligned unless noted; an output never aliases an input. */
+
+/* device: bev_conv2d_stem3_f32's arithmetic (fp32 images, weights and FMAs) with y [N][Ho][Wo][Co] stored in fp16:
+ * y = f16(bev_conv2d_stem3_f32's y), bit for bit. */
+int bev_conv2d_stem3_h16(const float *x, int N, int H, int W, const float *wt, const float *bias, int Co, int act,
+                         void *y, int Ho, int Wo, void *stream);
+
+/* device: depthwise KxK conv on fp16 storage: x [N][H][W][C] fp16, wt [K*K][C] fp16 tap-major, bias fp32;
+ *   y = f16( act( bias + sum_{ky,kx} float(x) float(wt) ) ),  fp32 fmaf chain from the bias, ky-major then kx-minor,
+ * zero padding exact.  C % 8 == 0, C <= 256, K in {3, 5}, stride in {1, 2}.  psum (optional) [N][nb][C] fp32, nb =
+ * bev_dwconv_h16_psum_blocks(Ho, Wo, C, stride): per-workgroup channel sums, in a fixed order, of the ROUNDED y. */
+int bev_dwconv_h16_psum_blocks(int Ho, int Wo, int C, int stride);
+int bev_dwconv2d_h16(const void *x, int N, int H, int W, int C, const void *wt, const float *bias, int K, int stride,
+                     int pad, int act, void *y, int Ho, int Wo, float *psum, void *stream);
+
+/* device: bev_ir_expand_dw_f32 on fp16 storage: x [N][H][W][Ci] fp16, we [Cm][Ci] fp16, wd [K*K][Cm] fp16 (2-B
+ * aligned), be / bd fp32;
+ *   h = f16( SiLU( sum_k x we + be ) )   on the fp16 matrix cores, fp32 accumulation; 0 outside the image; never stored
+ *   y = f16( SiLU( bd + sum_{ky,kx} float(h) float(wd) ) )   as bev_dwconv2d_h16
+ * psum [N][bev_ir_expand_dw_blocks(Ho, Wo, K, stride)][Cm]: sums of the rounded y.  Shapes as bev_ir_expand_dw_f32. */
+int bev_ir_expand_dw_h16(const void *x, int N, int H, int W, int Ci, const void *we, const float *be, int Cm,
+                         const void *wd, const float *bd, int K, int stride, void *y, int Ho, int Wo, float *psum,
+                         void *stream);
+
+/* device: 1x1 conv on fp16 storage, M = N H W pixels: x [M][Ci] fp16, w [Co][Ci] fp16, bias [Co] fp32 (or NULL),
+ * gate [N][Ci] fp32 (or NULL: the SE excitation, applied as the operand is loaded), residual [M][Co] fp16 (or NULL):
+ *   a = gate ? f16( float(x) * gate[n][k] ) : x
+ *   y[m][co] = ( sum_k a w  +  bias[co] )  +  float(residual[m][co])      fp32 accumulation on the fp16 matrix cores
+ * stored at y + m * ldy + co, rounded once to fp16 (y_half = 1) or as fp32 (y_half = 0).  Ci % 8 == 0, Ci <= 512,
+ * Co % 8 == 0, ldy >= Co, ldy % 8 == 0. */
+int bev_conv2d_pw_h16(const void *x, int N, int H, int W, int Ci, const void *w, const float *bias, const float *gate,
+                      const void *residual, int Co, void *y, int y_half, int ldy, void *stream);
+
 /* device: depthwise conv weight gradient (training): dW [K*K][C] (tap-major, like wt) =
  * sum over n, output pixels of dz[n][p][c] * x[n][tap t of p][c]; OVERWRITTEN (float atomics inside). */
 int bev_dwconv_wgrad_f32(const float *x, int N, int H, int W, int C, const float *dz, int Ho, int Wo, int K, int stride,

@@ -104,6 +104,11 @@ SIGNATURES = {
     "bev_se_gate_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "bev_conv2d_stem3_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "bev_ir_expand_dw_blocks": (_i, [_i, _i, _i, _i]),
+    "bev_conv2d_stem3_h16": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "bev_dwconv_h16_psum_blocks": (_i, [_i, _i, _i, _i]),
+    "bev_dwconv2d_h16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "bev_ir_expand_dw_h16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "bev_conv2d_pw_h16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "bev_ir_expand_dw_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "bev_channel_scale_f32": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
     "bev_decode_peaks_f32": (_i, [_vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
@@ -313,11 +318,15 @@ _AMP_LOCAL = threading.local()
 # the six partial products above 2^-27 relative on the bf16 matrix cores, fp32 accumulation: an fp32 convolution as
 # accurate as the exact-f32 MFMA kernels at 2.67x their matrix-core rate (tests/test_conv_x6_gpu.py measures both
 # against float64); "f32" = bev_conv2d_f32 and the chained bottleneck kernels (exact-f32 MFMA, bitwise an fmaf chain).
-# "f16" (opt-in; ResNet trunks) = bev_conv2d_h16_h16 -- what the reference's validation forward computes in eval()
-# under autocast(float16) (train.py:285-286): fp16 weights and activations on the fp16 matrix cores, fp32
-# accumulation, each conv output (after bias, residual and ReLU) rounded once to fp16 and kept in fp16 from layer to
-# layer; the stem stays in the split arithmetic and writes fp32 (wider than autocast), the encoder's 1x1 proj reads
-# the fp16 trunk output and writes fp32.  The default stays "bf16x6", also under autocast.
+# "f16" (opt-in) = what the reference's validation forward computes in eval() under autocast(float16)
+# (train.py:285-286): fp16 weights and activations on the fp16 matrix cores, fp32 accumulation, each layer's output
+# (after bias, residual and activation) rounded once to fp16 and kept in fp16 from layer to layer; the encoder's 1x1
+# proj reads the fp16 trunk output and writes fp32.  ResNet trunks: bev_conv2d_h16_h16, the stem in the split
+# arithmetic writing fp32 (wider than autocast).  EfficientNet trunks (b0-b3, features_only index <= 2;
+# EfficientNet.f16_applies): the fp32 stem storing fp16 (bev_conv2d_stem3_h16), bev_dwconv2d_h16,
+# bev_ir_expand_dw_h16 (the expanded tensor rounded to fp16 in LDS), the SE gate in fp32 from the stored values,
+# bev_conv2d_pw_h16 (gate applied as the operand is loaded); deeper indices keep the default arithmetic.
+# The default stays "bf16x6", also under autocast.
 CONV_ARITHS = ("f32", "bf16x6", "f16")
 _ARITH = {"mode": "bf16x6"}
 
@@ -1292,6 +1301,102 @@ def ir_expand_dw(x: torch.Tensor, we: torch.Tensor, be: torch.Tensor, wd: torch.
                                         _ptr(psum), _stream(x))
     _check(rc, "bev_ir_expand_dw_f32")
     return y, psum
+
+
+def conv2d_stem3_h16(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, act: int) -> torch.Tensor:
+    """conv2d_stem3 with the output stored in fp16 (bev_conv2d_stem3_h16): bitwise conv2d_stem3(...).half()."""
+    x = x.contiguous()
+    _require_gpu(x, wt, bias)
+    N, Ci, H, W = x.shape
+    Co = wt.shape[1]
+    if Ci != 3 or wt.shape[0] != 27:
+        raise HipError("conv2d_stem3_h16 takes 3-channel images and a [27, Co] weight")
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float16)
+    with _span("conv", x):
+        rc = lib().bev_conv2d_stem3_h16(_ptr(x), N, H, W, _ptr(wt.contiguous()), _ptr(bias.contiguous()), Co, int(act),
+                                        _ptr(y), Ho, Wo, _stream(x))
+    _check(rc, "bev_conv2d_stem3_h16")
+    return y
+
+
+def _require_h16(who, halves, floats):
+    """The fp16-storage EfficientNet kernels: `halves` are fp16 device tensors, `floats` fp32 ones (None allowed)."""
+    _require_gpu(*halves, dtypes=(torch.float16,), what=f"{who}: fp16")
+    _require_gpu(*floats, dtypes=(torch.float32,), what=f"{who}: fp32")
+
+
+def dwconv2d_nhwc_h16(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, K: int, stride: int, pad: int, act: int,
+                      want_psum: bool = False):
+    """dwconv2d_nhwc on fp16 storage (bev_dwconv2d_h16): x [N,H,W,C] fp16, wt [K*K, C] fp16 tap-major, bias [C] fp32
+    -> y [N,Ho,Wo,C] fp16 (fp32 fmaf chain, rounded once) and, with want_psum, the fp32 SE partial sums [N, nb, C] of
+    the rounded y."""
+    x = x.contiguous()
+    _require_h16("dwconv2d_nhwc_h16", (x, wt), (bias,))
+    N, H, W, C = x.shape
+    Ho, Wo = _out_hw(H, W, K, K, stride, pad)
+    y = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float16)
+    psum = None
+    if want_psum:
+        nb = lib().bev_dwconv_h16_psum_blocks(Ho, Wo, C, stride)
+        _check(0 if nb > 0 else nb, "bev_dwconv_h16_psum_blocks")
+        psum = torch.empty(N, nb, C, device=x.device, dtype=torch.float32)
+    with _span("dwconv", x):
+        rc = lib().bev_dwconv2d_h16(_ptr(x), N, H, W, C, _ptr(wt.contiguous()), _ptr(bias.contiguous()), K, stride, pad,
+                                    int(act), _ptr(y), Ho, Wo, _ptr(psum), _stream(x))
+    _check(rc, "bev_dwconv2d_h16")
+    return y, psum
+
+
+def ir_expand_dw_h16(x: torch.Tensor, we: torch.Tensor, be: torch.Tensor, wd: torch.Tensor, bd: torch.Tensor, K: int,
+                     stride: int):
+    """ir_expand_dw on fp16 storage (bev_ir_expand_dw_h16): x [N,H,W,Ci] fp16, we [Cm, Ci] fp16, wd [K*K, Cm] fp16,
+    be / bd [Cm] fp32 -> (y [N,Ho,Wo,Cm] fp16, fp32 SE partial sums [N, nb, Cm] of the rounded y).  The expanded
+    tensor is rounded to fp16 in LDS and never stored."""
+    x = x.contiguous()
+    _require_h16("ir_expand_dw_h16", (x, we, wd), (be, bd))
+    N, H, W, Ci = x.shape
+    Cm = we.shape[0]
+    Ho, Wo = _out_hw(H, W, K, K, stride, K // 2)
+    nb = lib().bev_ir_expand_dw_blocks(Ho, Wo, K, stride)
+    _check(0 if nb > 0 else nb, "bev_ir_expand_dw_blocks")
+    y = torch.empty(N, Ho, Wo, Cm, device=x.device, dtype=torch.float16)
+    psum = torch.empty(N, nb, Cm, device=x.device, dtype=torch.float32)
+    with _span("dwconv", x):
+        rc = lib().bev_ir_expand_dw_h16(_ptr(x), N, H, W, Ci, _ptr(we.contiguous()), _ptr(be.contiguous()), Cm,
+                                        _ptr(wd.contiguous()), _ptr(bd.contiguous()), K, stride, _ptr(y), Ho, Wo,
+                                        _ptr(psum), _stream(x))
+    _check(rc, "bev_ir_expand_dw_h16")
+    return y, psum
+
+
+def conv2d_pw_h16(x: torch.Tensor, w: torch.Tensor, bias, gate=None, residual=None, f32_out: bool = False,
+                  out: torch.Tensor = None) -> torch.Tensor:
+    """1x1 conv on fp16 storage (bev_conv2d_pw_h16): x [N,H,W,Ci] fp16 NHWC, w [Co, Ci] fp16, bias [Co] fp32 or None,
+    gate [N, Ci] fp32 or None (a = f16(float(x) * gate) as the operand is loaded), residual [N,H,W,Co] fp16 or None
+    -> y [N,H,W,Co] fp16, or fp32 with f32_out.  `out`: a [N,H,W,ldy >= Co] device tensor of the output type to write
+    into (columns >= Co are left as they are)."""
+    x = x.contiguous()
+    _require_h16("conv2d_pw_h16", (x, w, residual), (bias, gate))
+    N, H, W, Ci = x.shape
+    Co = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != Ci:
+        raise HipError("conv2d_pw_h16: w is [Co, Ci]")
+    if gate is not None and (tuple(gate.shape) != (N, Ci) or not gate.is_contiguous()):
+        raise HipError("conv2d_pw_h16: gate is a contiguous [N, Ci] tensor")
+    if residual is not None and (tuple(residual.shape) != (N, H, W, Co) or not residual.is_contiguous()):
+        raise HipError("conv2d_pw_h16: the residual is a dense fp16 NHWC tensor of the output's shape")
+    odt = torch.float32 if f32_out else torch.float16
+    if out is None:
+        out = torch.empty(N, H, W, Co, device=x.device, dtype=odt)
+    elif (not out.is_cuda or out.dtype != odt or out.dim() != 4 or tuple(out.shape[:3]) != (N, H, W)
+          or out.shape[3] < Co or not out.is_contiguous()):
+        raise HipError("conv2d_pw_h16: out is a contiguous [N, H, W, ldy >= Co] device tensor of the output's type")
+    with _span("conv", x):
+        rc = lib().bev_conv2d_pw_h16(_ptr(x), N, H, W, Ci, _ptr(w.contiguous()), _ptr(bias), _ptr(gate), _ptr(residual),
+                                     Co, _ptr(out), int(not f32_out), out.shape[3], _stream(x))
+    _check(rc, "bev_conv2d_pw_h16")
+    return out
 
 
 def se_gate(psum: torch.Tensor, hw: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor):

@@ -487,11 +487,14 @@ constexpr int S3_TR = 8, S3_TC = 64;                          // output tile row
 constexpr int S3_IR = 2 * S3_TR + 1, S3_IC = 2 * S3_TC + 1;  // its input window (stride 2, 3 taps)
 constexpr int S3_ICP = S3_IC + 3;                             // padded window row (floats)
 
+typedef _Float16 irh8 __attribute__((ext_vector_type(8)));
 int g_stem3_stage = 2;  // BEV_TUNE_STEM3_STAGE (r06u micro, 14 x 1080p B3 stem: 64-pixel passes 545 us, 32-pixel 481, registers 3483)
 
-template <int CO, int SP>  // SP: output pixels staged per wave and pass (64 / 32), 0 = stores from registers
+// OT = _Float16 ("f16" inference arithmetic, bev_conv2d_stem3_h16; SP > 0): the same fp32 values, rounded once as the
+// staged run is stored (8 channels, 16 B per lane).
+template <int CO, int SP, typename OT = float>  // SP: output pixels staged per wave and pass (64 / 32), 0 = stores from registers
 __global__ __launch_bounds__(256) void k_stem3(const float *__restrict__ x, int H, int W, const float *__restrict__ wt,
-                                               const float *__restrict__ bias, int act, float *__restrict__ y, int Ho,
+                                               const float *__restrict__ bias, int act, OT *__restrict__ y, int Ho,
                                                int Wo, int tiles_x) {
     constexpr int CP = CO + 1;                 // staged pixel stride (odd: conflict-free dword writes)
     constexpr int IN_F = 3 * S3_IR * S3_ICP;   // input window floats
@@ -540,7 +543,7 @@ __global__ __launch_bounds__(256) void k_stem3(const float *__restrict__ x, int 
                     acc1[c] = __builtin_fmaf(v1, wt[t * CO + c], acc1[c]);
                 }
             }
-    if constexpr (SP == 0) {  // straight from registers: 16 B per lane, lanes a pixel (CO floats) apart
+    if constexpr (SP == 0 && sizeof(OT) == 4) {  // straight from registers: 16 B per lane, lanes a pixel (CO floats) apart
         const int c = c0 + lane;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -574,11 +577,22 @@ __global__ __launch_bounds__(256) void k_stem3(const float *__restrict__ x, int 
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const int np = min(SP, Wo - c0 - hb * SP);  // pixels of this run piece
             if (r < Ho && np > 0) {
-                float *dst = y + (((int64_t)n * Ho + r) * Wo + c0 + hb * SP) * CO;
-                for (int f = lane * 4; f < np * CO; f += 256) {  // CO % 4 == 0: a quad never straddles two pixels
-                    const int p = f / CO, c = f - p * CO;
-                    const float *s = stg + p * CP + c;
-                    *(float4 *)(dst + f) = make_float4(s[0], s[1], s[2], s[3]);
+                OT *dst = y + (((int64_t)n * Ho + r) * Wo + c0 + hb * SP) * CO;
+                if constexpr (sizeof(OT) == 4) {
+                    for (int f = lane * 4; f < np * CO; f += 256) {  // CO % 4 == 0: a quad never straddles two pixels
+                        const int p = f / CO, c = f - p * CO;
+                        const float *s = stg + p * CP + c;
+                        *(float4 *)(dst + f) = make_float4(s[0], s[1], s[2], s[3]);
+                    }
+                } else {
+                    for (int f = lane * 8; f < np * CO; f += 512) {  // CO % 8 == 0: an octet never straddles two pixels
+                        const int p = f / CO, c = f - p * CO;
+                        const float *s = stg + p * CP + c;
+                        irh8 o;
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) o[u] = (_Float16)s[u];
+                        *(irh8 *)(dst + f) = o;
+                    }
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -909,6 +923,28 @@ int bev_conv2d_stem3_f32(const float *x, int N, int H, int W, const float *wt, c
     else if (Co == 48) STEM3_LAUNCH(48);
     else STEM3_LAUNCH(64);
 #undef STEM3_LAUNCH
+    return last();
+}
+
+int bev_conv2d_stem3_h16(const float *x, int N, int H, int W, const float *wt, const float *bias, int Co, int act,
+                         void *y, int Ho, int Wo, void *stream) {
+    if (!x || !wt || !bias || !y || N < 0 || H <= 0 || W <= 0 || act < 0 || act > 2 ||
+        (Co != 32 && Co != 40 && Co != 48 && Co != 64))
+        return BEV_ERR_ARGS;
+    if (Ho != (H - 1) / 2 + 1 || Wo != (W - 1) / 2 + 1 || (((uintptr_t)y) & 15) != 0) return BEV_ERR_ARGS;
+    if ((int64_t)3 * H * W >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
+    if (N == 0) return 0;
+    const int tiles_x = (Wo + S3_TC - 1) / S3_TC, tiles = ((Ho + S3_TR - 1) / S3_TR) * tiles_x;
+    const dim3 grid(tiles, N);
+    hipStream_t st = (hipStream_t)stream;
+    _Float16 *yh = (_Float16 *)y;
+    // always the 32-pixel staged store (the fp32 entry's default, BEV_TUNE_STEM3_STAGE 2)
+#define STEM3_H16(CO) hipLaunchKernelGGL((k_stem3<CO, 32, _Float16>), grid, dim3(256), 0, st, x, H, W, wt, bias, act, yh, Ho, Wo, tiles_x)
+    if (Co == 32) STEM3_H16(32);
+    else if (Co == 40) STEM3_H16(40);
+    else if (Co == 48) STEM3_H16(48);
+    else STEM3_H16(64);
+#undef STEM3_H16
     return last();
 }
 

@@ -75,7 +75,17 @@ class CNNEncoder(ViewEncoder):
             )
         self._fb = None
         self._fproj = None
+        self._proj_h16_key = None
         self.proj_stream_nt = True  # non-temporal activation loads in the inference projection (see forward)
+
+    def _proj_h16(self, device):
+        p = self.proj
+        key = (p.weight.data_ptr(), p.weight._version, p.bias.data_ptr(), p.bias._version, str(device))
+        if self._proj_h16_key != key:
+            self._proj_h16_wb = (p.weight.detach().to(device).reshape(p.out_channels, -1).half().contiguous(),
+                                 p.bias.detach().to(device).float().contiguous())
+            self._proj_h16_key = key
+        return self._proj_h16_wb
 
     def _trunk_frozen(self) -> bool:
         return not any(p.requires_grad for p in self.backbone.parameters())
@@ -98,6 +108,10 @@ class CNNEncoder(ViewEncoder):
                 return Proj1x1.apply(feat, self.proj.weight, self.proj.bias)  # trainable proj (BASELINE config 3)
             if self._fproj.arith() == "f16":
                 return self._fproj(feat, relu=False, f32_out=True)
+            if feat.dtype == torch.float16:
+                # an EfficientNet trunk in the "f16" arithmetic: the proj reads its fp16 output with fp16 weights
+                # (rounded once, cached apart from the default mode's panel) and writes fp32
+                return _nat.conv2d_pw_h16(feat, *self._proj_h16(feat.device), f32_out=True)
             if self.proj_stream_nt:
                 # The projection is the last reader of the trunk output (~8x the feature maps' bytes): streamed
                 # with non-temporal loads it no longer evicts the maps it writes from the Infinity Cache, and the

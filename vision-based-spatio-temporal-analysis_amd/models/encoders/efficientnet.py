@@ -24,6 +24,12 @@ squeeze partials fused), the SE gate is `bev_se_gate_f32`, and the excitation
 `x * gate` is applied inside the projection conv's operand load (`bev_conv2d_chscale_f32`), which also adds
 the skip in its epilogue.
 
+"f16" inference arithmetic (bev_native.conv_arith_mode("f16"), eval, features_only index <= 2: `f16_applies`): the same
+graph on fp16 storage -- the stem's fp32 result stored in fp16, bev_dwconv2d_h16, bev_ir_expand_dw_h16, the SE gate
+in fp32 from the stored values, bev_conv2d_pw_h16 with the gate applied as its operand is loaded and the fp16 skip in
+its epilogue; the BN-folded weights rounded once to fp16 (cached under their own keys), fp32 accumulation, every
+stored value rounded once.  Deeper indices keep the default arithmetic.
+
 Training (model.train()): the same graph on autograd nodes with native backward kernels (trunk_grad.py:
 ConvBNTrain with SiLU, DWConvBNTrain, SqueezeExcite); BN with batch statistics.
 """
@@ -201,6 +207,85 @@ class EfficientNet(nn.Module):
         dw = blk.conv_dw
         return _nat.ir_expand_dw(x, ent[1], ent[2], fdw.wt, fdw.bias, dw.kernel_size[0], dw.stride[0])
 
+    # ---- the "f16" inference arithmetic -------------------------------------------------------------------------
+    def _stem3_shape(self) -> bool:
+        c = self.conv_stem
+        return (self.stem3 and c.in_channels == 3 and c.kernel_size == (3, 3) and c.stride == (2, 2)
+                and c.padding == (1, 1) and c.groups == 1 and c.dilation == (1, 1) and c.out_channels in (32, 40, 48, 64))
+
+    def f16_applies(self, out_index: int) -> bool:
+        """Does features_only[out_index] run in the "f16" arithmetic under conv_arith_mode("f16")?  True when the stem
+        and every block up to that index meet the fp16 kernels' rules: the stem3 shape; depthwise-separable blocks
+        with C % 8 == 0, C <= 256, K in {3, 5}, stride in {1, 2}; inverted residuals that take the fused
+        expansion + depthwise kernel (`ir_fused_block`); projections with Ci % 8 == 0, Ci <= 512, Co % 8 == 0.  For
+        efficientnet_b0 .. b3 that is out_index 0, 1, 2; 3 and 4 (80-channel inputs) keep the default arithmetic."""
+        if out_index not in FEATURE_STAGE or not self._stem3_shape():
+            return False
+        cin = self.conv_stem.out_channels
+        for si in range(FEATURE_STAGE[out_index] + 1):
+            for blk in self.blocks[si]:
+                if isinstance(blk, DepthwiseSeparableConv):
+                    dw, pw = blk.conv_dw, blk.conv_pw
+                    if not (cin % 8 == 0 and cin <= 256 and dw.kernel_size in ((3, 3), (5, 5))
+                            and dw.stride in ((1, 1), (2, 2)) and dw.padding == (dw.kernel_size[0] // 2,) * 2
+                            and dw.groups == dw.in_channels == cin and dw.dilation == (1, 1)):
+                        return False
+                else:
+                    if not self.ir_fused_block(blk, cin):
+                        return False
+                    pw = blk.conv_pwl
+                if not (pw.kernel_size == (1, 1) and pw.stride == (1, 1) and pw.groups == 1
+                        and pw.in_channels % 8 == 0 and pw.in_channels <= 512 and pw.out_channels % 8 == 0):
+                    return False
+                cin = pw.out_channels
+        return True
+
+    def _h16(self, kind, conv, bn, device):
+        """fp16 operands of one conv + BN in the "f16" arithmetic: folded in fp32, rounded once; cached under
+        ("h16", kind, id(conv)), apart from the default mode's folded weights.  kind "pw": (w [Co, Ci] fp16, b fp32);
+        "dw": (wt [K*K, C] fp16 tap-major, b); "stem": (wt [27, Co] fp32, b) -- the stem's arithmetic stays fp32."""
+        fc = self._fc(conv, bn)
+        key = ("h16", kind, id(conv))
+        tkey = tuple((t.data_ptr(), t._version) for t in fc._tensors()) + (str(device),)
+        ent = self._folded.get(key)
+        if ent is None or ent[0] != tkey:
+            w, b = fc.folded(device)
+            if kind == "pw":
+                w = w.reshape(w.shape[0], -1).half().contiguous()
+            elif kind == "dw":
+                w = w.reshape(w.shape[0], -1).t().half().contiguous()
+            else:
+                w = w.permute(1, 2, 3, 0).reshape(27, w.shape[0]).contiguous()
+            ent = (tkey, w, b.contiguous().float())
+            self._folded[key] = ent
+        return ent[1], ent[2]
+
+    def _block_f16(self, blk, x):
+        dev = x.device
+        if isinstance(blk, DepthwiseSeparableConv):
+            dw = blk.conv_dw
+            wd, bd = self._h16("dw", dw, blk.bn1, dev)
+            y, ps = _nat.dwconv2d_nhwc_h16(x, wd, bd, dw.kernel_size[0], dw.stride[0], dw.padding[0], _nat.ACT_SILU,
+                                           want_psum=True)
+            proj, bnp = blk.conv_pw, blk.bn2
+        else:
+            dw = blk.conv_dw
+            we, be = self._h16("pw", blk.conv_pw, blk.bn1, dev)
+            wd, bd = self._h16("dw", dw, blk.bn2, dev)
+            y, ps = _nat.ir_expand_dw_h16(x, we, be, wd, bd, dw.kernel_size[0], dw.stride[0])
+            proj, bnp = blk.conv_pwl, blk.bn3
+        wp, bp = self._h16("pw", proj, bnp, dev)
+        return _nat.conv2d_pw_h16(y, wp, bp, gate=self._gate(blk.se, y, ps), residual=x if blk.has_skip else None)
+
+    def _forward_f16(self, x, out_index):
+        with torch.no_grad():
+            wt, b = self._h16("stem", self.conv_stem, self.bn1, x.device)
+            y = _nat.conv2d_stem3_h16(x, wt, b, _nat.ACT_SILU)
+            for si in range(FEATURE_STAGE[out_index] + 1):
+                for blk in self.blocks[si]:
+                    y = self._block_f16(blk, y)
+        return y
+
     def _fc_expand(self, conv, bn):
         """The inverted-residual expansion (1x1, Ci -> 6 Ci, SiLU): on the split-bf16 kernels (bev_conv2d_x6_f32, fp32
         class) when `x6_expand` and the arithmetic is bf16x6 and Ci % 16 == 0, else as _fc."""
@@ -249,11 +334,14 @@ class EfficientNet(nn.Module):
                 for n, _ in self.blocks[si].named_parameters()]
 
     def forward_features_nhwc(self, x: torch.Tensor, out_index: int) -> torch.Tensor:
-        """x: images [N,3,H,W] NCHW fp32 on the device -> NHWC features_only[out_index]."""
+        """x: images [N,3,H,W] NCHW fp32 on the device -> NHWC features_only[out_index] (fp32; fp16 in the "f16"
+        inference arithmetic where `f16_applies`)."""
         if out_index not in FEATURE_STAGE:
             raise IndexError(f"efficientnet feature index {out_index} out of range 0..4")
         if self.training:  # torch semantics: train-mode BN uses batch statistics, with or without autograd
             return self._forward_train(x, out_index)
+        if _nat.conv_arith() == "f16" and self.f16_applies(out_index):
+            return self._forward_f16(x, out_index)
         y = self._stem(x)
         # inference: every tiny-K (Ci 24-48) 1x1 conv on the wave-streaming k_pw_mfma (BEV_TUNE_CONV_PW_SMALL 3), the
         # wide expansions included; training keeps the default (2: narrow outputs only), whose k order the float64
