@@ -611,7 +611,12 @@ int bev_conv_pack_weights_x6(const float *w, int Co, int Ci, int KH, int KW, uin
  * (residual needs ldy == Co).  Output fp32 y, or, with y NULL, the result split into ys [3][N][Ho][Wo][Co] bf16
  * planes (ldy == Co, Co % 4 == 0) -- the pre-split operand of the next conv.  Replaces the nn.Conv2d (+ folded
  * eval BN) layers of the timm trunk and the lazy 1x1 projection (cnn_encoder.py:26,41-46) -- the contract of
- * bev_conv2d_f32 for NHWC inputs. */
+ * bev_conv2d_f32 for NHWC inputs.
+ * Input limit: finite operands (x, weights) with |v| < 0x7F7F8000 (~3.396e38; FLT_MAX is past it).  bf16(v) of a
+ * larger finite value is Inf and the split's residual v - Inf is NaN, as it is for v = +-Inf: such an operand, like a
+ * NaN, makes every output of its receptive field NaN (where bev_conv2d_f32 gives +-Inf or a finite number) and no
+ * other -- non-finite in, non-finite out, never a finite wrong number; the ReLU keeps a NaN (as torch.relu does).
+ * The same holds for every *_x6_f32 entry below. */
 int bev_conv2d_x6_f32(const float *x, const uint16_t *xs, int N, int H, int W, int Ci, const uint16_t *packed,
                       const float *bias, const float *residual, int Co, int KH, int KW, int stride, int pad,
                       int dilation, int act, float *y, uint16_t *ys, int ldy, int Ho, int Wo, void *stream);

@@ -320,7 +320,7 @@ __global__ void k_bn_apply(const float *__restrict__ z, int C, const float *__re
             const float4 r = *(const float4 *)(res + e);
             o = make_float4(o.x + r.x, o.y + r.y, o.z + r.z, o.w + r.w);
         }
-        if (act == 1) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+        if (act == 1) o = make_float4(relu_f(o.x), relu_f(o.y), relu_f(o.z), relu_f(o.w));
         if (act == 2)  // torch SiLU: x / (1 + exp(-x))
             o = make_float4(silu_hw(o.x), silu_hw(o.y), silu_hw(o.z), silu_hw(o.w));
         st4(y, e, o);
@@ -379,7 +379,7 @@ __device__ __forceinline__ void bn_apply_one(const float4 v, const float4 rr, co
                                              uint8_t *mask, int64_t e) {
     float4 o = make_float4(bn_u(v.x, s.x, h.x), bn_u(v.y, s.y, h.y), bn_u(v.z, s.z, h.z), bn_u(v.w, s.w, h.w));
     if constexpr (RES) o = make_float4(o.x + rr.x, o.y + rr.y, o.z + rr.z, o.w + rr.w);
-    if constexpr (ACT == 1) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+    if constexpr (ACT == 1) o = make_float4(relu_f(o.x), relu_f(o.y), relu_f(o.z), relu_f(o.w));
     if constexpr (ACT == 2) o = make_float4(silu_hw(o.x), silu_hw(o.y), silu_hw(o.z), silu_hw(o.w));
     st4(y, e, o);
     if (mask)  // act 1: bit u = (y[e + u] > 0), what the backward's act 4 reads instead of y

@@ -69,7 +69,7 @@ __global__ void k_pack(const float *__restrict__ w, int Co, int Ci, int KH, int 
 // Epilogue activation: 1 = ReLU, 2 = SiLU (torch: x / (1 + exp(-x)); EfficientNet trunk).
 __device__ __forceinline__ float act_fn(float t, int act) {
     if (act == 2) return silu_hw(t);
-    return t > 0.0f ? t : 0.0f;
+    return relu_f(t);
 }
 
 struct ConvArgs {  // conv_args fills the geometry; an entry point sets what is particular to it over these defaults
@@ -204,7 +204,7 @@ struct LoaderFastEx : LoaderFast<ROWS> {
                 const int64_t o = (int64_t)rows.img[r] * a.Ci + ci0 + quad * 4;
                 v[r] *= *(const f32x4 *)(a.ascale + o);
                 if (a.ashift) v[r] += *(const f32x4 *)(a.ashift + o);
-                if (a.arelu) v[r] = __builtin_elementwise_max(v[r], (f32x4){0.f, 0.f, 0.f, 0.f});
+                if (a.arelu) v[r] = __builtin_elementwise_maximum(v[r], (f32x4){0.f, 0.f, 0.f, 0.f});
             }
         }
         if (a.ascale && rows.uni) {
@@ -218,7 +218,7 @@ struct LoaderFastEx : LoaderFast<ROWS> {
 #pragma unroll
                 for (int r = 0; r < ROWS; ++r) {
                     f32x4 t = v[r] * g + sh;
-                    if (a.arelu) t = __builtin_elementwise_max(t, (f32x4){0.f, 0.f, 0.f, 0.f});
+                    if (a.arelu) t = __builtin_elementwise_maximum(t, (f32x4){0.f, 0.f, 0.f, 0.f});
                     v[r] = inr[r] ? t : v[r];  // zero padding is applied after the normalisation
                 }
             }
@@ -1065,8 +1065,8 @@ __global__ __launch_bounds__(256, 2) void k_stem(StemArgs a) {
                         if (ox < a.Wo) {
                             float v0 = c0[r] + b0, v1 = c1[r] + b1;
                             if (a.relu) {
-                                v0 = v0 > 0.0f ? v0 : 0.0f;
-                                v1 = v1 > 0.0f ? v1 : 0.0f;
+                                v0 = relu_f(v0);
+                                v1 = relu_f(v1);
                             }
                             float *yp = yr + (int64_t)ox * a.Co;
                             if (r32 < a.Co) yp[r32] = v0;

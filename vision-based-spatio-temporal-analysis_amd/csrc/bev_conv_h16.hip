@@ -75,7 +75,7 @@ struct ConvH {
 
 __device__ __forceinline__ float act_h(float t, int act) {
     if (act == 2) return silu_hw(t);
-    if (act == 1) return t > 0.0f ? t : 0.0f;
+    if (act == 1) return relu_f(t);
     return t;
 }
 
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
                     }                                                                                      \
                     _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                        \
                         float f_ = (float)v_[e] * (e < 4 ? s0[e & 3] : s1[e & 3]) + (e < 4 ? t0[e & 3] : t1[e & 3]); \
-                        if (a.in_relu) f_ = fmaxf(f_, 0.f);                                                \
+                        if (a.in_relu) f_ = relu_f(f_);                                                    \
                         v_[e] = (_Float16)f_;                                                              \
                     }                                                                                      \
                 }                                                                                          \

@@ -6,7 +6,15 @@
 // values by round-to-nearest-even splitting:
 //     h = bf16(v),  m = bf16(v - h),  l = bf16(v - h - m)        v == h + m + l  (8 + 8 + 8 significand bits;
 // both subtractions are exact in fp32 because each residual is a multiple of ulp(v) below half an ulp of the
-// previous term), |m| <= 2^-9 |v|, |l| <= 2^-18 |v|.  A product a*b is then the sum of nine bf16 x bf16
+// previous term), |m| <= 2^-9 |v|, |l| <= 2^-18 |v|.
+// Range of "EXACTLY" (tests/test_conv_value_domain_gpu.py): finite |v| < 0x7F7F8000 (~3.396e38) whose pieces stay
+// bf16 / fp32 normals.  |v| >= 0x7F7F8000 (FLT_MAX is one) rounds to h = Inf, and then, as for v = +-Inf, r = v - h
+// is NaN: a non-finite operand, or a finite one past that limit, gives NaN (not +-Inf) in every output of its
+// receptive field and nowhere else -- non-finite in, non-finite out, never a finite wrong number (the ReLU epilogues
+// keep a NaN, bev_act.h).  Measured on an MI355X: operands scaled by 2^-30 .. 2^30 each (outputs 2^-60 .. 2^60 times
+// unit scale) give bit-identical scaled outputs; at 2^-50 x 2^-50 (outputs ~2^-100, the low planes' products fp32
+// subnormal) and 2^50 x 2^50 the result still meets the 1e-5 max|ref| float64 bar (5.5e-7 seen, as at unit scale).
+// A product a*b is then the sum of nine bf16 x bf16
 // products, each EXACT in fp32; the six kept here are those larger than 2^-27 |a b|:
 //     hh + hm + mh + hl + lh + mm          (dropped: ml + lm + ll <= 2^-26 |a b|, below fp32's 2^-24 rounding)
 // and all of them accumulate into the fp32 MFMA accumulator.  The result is an fp32 GEMM whose per-product error
@@ -112,7 +120,7 @@ struct ConvX {  // conv_x6_args fills the geometry; an entry point sets what is 
 template <int ACT>
 __device__ __forceinline__ float act_c(float t) {
     if constexpr (ACT == 2) return silu_hw(t);
-    else if constexpr (ACT == 1) return t > 0.0f ? t : 0.0f;
+    else if constexpr (ACT == 1) return relu_f(t);
     else return t;
 }
 
@@ -1192,13 +1200,15 @@ __device__ __forceinline__ void stem6_put(float *pl, int tid, const float (&pv)[
     }
 }
 
-// the pooled maximum of relu'd stem values (>= +0, never NaN: the ReLU maps NaN to 0)
-__device__ __forceinline__ float pool_mx(float m, float v) { return __builtin_fmaxf(m, v); }
+// the pooled maximum of relu'd stem values (>= +0, or NaN: the ReLU keeps a NaN and so does this maximum, as
+// k_maxpool_rows and torch's max_pool2d do)
+__device__ __forceinline__ float pool_mx(float m, float v) { return max_nan(m, v); }
 
 // POOL: timm's stem max-pool (3x3 / s2 / p1, cnn_encoder.py:26 features_only) fused into the epilogue.  The stem
 // output is relu'd (>= +0), so a window's padding and the tile's rows / columns past the image may count as +0 without
 // changing any maximum: every pooled value is the max over a set of non-negative values, whatever the grouping --
-// bit-identical to k_maxpool_rows over the stem output.  Tile (ty, tx) = stem rows 8ty..8ty+7 x columns
+// bit-identical to k_maxpool_rows over the stem output.  A NaN stem value (a NaN or Inf pixel under it) makes every
+// pooled value whose window holds it NaN, in any grouping too: pool_mx keeps a NaN, as k_maxpool_rows does.  Tile (ty, tx) = stem rows 8ty..8ty+7 x columns
 // 64tx..64tx+63 owns pooled rows 4ty..4ty+3 x columns 32tx..32tx+31; pooled row 4ty needs stem row 8ty-1 (tile ty-1)
 // and pooled column 32tx stem column 64tx-1 (tile tx-1): each tile stores its own part of those seam outputs and
 // exports its last row / column parts (edge_b / edge_r), which k_stem_pool_seams folds in afterwards.
@@ -1300,7 +1310,7 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                         for (int u = 0; u < 4; ++u) {
                             const int ox = oxb + 32 * mt + 8 * b + 4 * h + u;
                             const float z = acc[mt][j][4 * b + u] + (j ? b1 : b0);
-                            v[u] = oy < a.Ho && ox < a.Wo && z > 0.0f ? z : 0.0f;  // the stem's ReLU (NaN -> 0)
+                            v[u] = oy < a.Ho && ox < a.Wo ? relu_f(z) : 0.0f;  // the stem's ReLU (a NaN stays)
                         }
                         pa3[mt][j][b] = __shfl_xor(v[3], 32);
                         hp[mt][b][1][j] = pool_mx(pool_mx(v[1], v[2]), v[3]);
@@ -1407,8 +1417,8 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                         if (ox < a.Wo) {
                             float v0 = acc[mt][0][r] + b0, v1 = acc[mt][1][r] + b1;
                             if (a.relu) {
-                                v0 = v0 > 0.0f ? v0 : 0.0f;
-                                v1 = v1 > 0.0f ? v1 : 0.0f;
+                                v0 = relu_f(v0);
+                                v1 = relu_f(v1);
                             }
                             float *yp = yr + (int64_t)ox * a.Co;
                             if (r32 < a.Co) yp[r32] = v0;

@@ -37,7 +37,7 @@ inline int dw_ch4(int C) { return C / 4 <= DW_NT ? C / 4 : DW_NT / 2; }
 inline int dw_ppb(int C) { return DW_STEPS * (DW_NT / dw_ch4(C)); }
 
 __device__ __forceinline__ float act_f(float t, int act) {
-    if (act == 1) return t > 0.0f ? t : 0.0f;
+    if (act == 1) return relu_f(t);
     if (act == 2) return silu_hw(t);  // torch SiLU x / (1 + exp(-x)), hardware exp2 / rcp (bev_act.h)
     return t;
 }

@@ -27,7 +27,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float act_f(float t, int act) {
-    if (act == 1) return t > 0.0f ? t : 0.0f;
+    if (act == 1) return relu_f(t);
     if (act == 2) return silu_hw(t);
     return t;
 }

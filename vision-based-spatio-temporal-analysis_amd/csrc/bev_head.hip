@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/bev_mi355x.h"
+#include "bev_act.h"
 
 namespace {
 
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(GN_T) void k_gn_apply(const float *__restrict__ x, 
         const int64_t e = base + p * C;
         const float4 v = *(const float4 *)(x + e);
         float4 o = make_float4(v.x * s.x + h.x, v.y * s.y + h.y, v.z * s.z + h.z, v.w * s.w + h.w);
-        if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+        if (relu) o = make_float4(relu_f(o.x), relu_f(o.y), relu_f(o.z), relu_f(o.w));
         gn_st4(y, e, o);
     }
 }
