@@ -34,7 +34,9 @@ extern "C" {
 #define BEV_FUSE_MAX 2
 
 /* 16: the pre-split chain that also ran the next block's 1x1 conv in its epilogue left (last tree: 5535b89).
- * ABI version (bumped on any signature change): 16. */
+ * 17: the depthwise kernels that only a non-default knob could launch left, with the knob values that selected them
+ *     (DW_RUN 1 / 2); CONV_X6_KERNEL 2, an alias of 0, is rejected (last tree: e891532).
+ * ABI version (bumped on any signature change, and when public constants or accepted values go): 17. */
 int bev_abi_version(void);
 
 /* host: provenance -- the first 16 hex digits of sha256 over the library's HIP sources and headers (the
@@ -61,7 +63,7 @@ const char *bev_build_source_hash(void);
  *   results bit for bit.
  * BEV_TUNE_CONV_X6_TILE: output tile of the split-bf16 fp32 convs (bev_conv2d_x6_f32 / _dual_x6_f32):
  *   0 = automatic, 1 = 128x128, 2 = 128x64.
- * BEV_TUNE_CONV_X6_KERNEL: 0 (default) / 2 = 32-deep K steps with B fragments read straight from the panel
+ * BEV_TUNE_CONV_X6_KERNEL: 0 (default) = 32-deep K steps with B fragments read straight from the panel
  *   wherever Ci (and Ci2) % 32 == 0, 1 = the 16-deep-step kernel (both operands through LDS) for every shape.
  *   Same results bit for bit.
  * BEV_TUNE_CONV_H16_KERNEL: autocast fp16 convs: 0 (default) = 64-deep K steps, two steps in flight, where Ci % 64 ==
@@ -77,10 +79,14 @@ const char *bev_build_source_hash(void);
  *   Ci in {24, 32, 40, 48} and Co <= 32 on a wave-streaming MFMA kernel (k_pw_mfma, float4 epilogue through
  *   LDS); 3 = every 1x1 with Ci in {24, 32, 40, 48} on it (faster inference); 4 = as 2 with dword stores.
  *   All fp32-tolerance equal.
- * BEV_TUNE_DW_RUN: depthwise convs with <= 256 channels that the LDS tile does not take: 0 = per pixel (k_dwconv),
- *   1 = row runs (k_dwconv_r), 2 = row runs with the 3 x 3 rows' loads issued up front, 3 (default) = 2 for every
- *   width (also where the LDS tile k_dwconv_t ran).  Same y up to the sign of an exact zero; the SE partial count
- *   per bev_dwconv_psum_blocks, which follows the knob.
+ * BEV_TUNE_DW_RUN: depthwise convs: 3 (default) = row runs (k_dwconv_r, the 3 x 3 rows' loads issued up front) for
+ *   stride 1 / 2 wherever C / 4 splits into equal chunks of at most 64 quads (every multiple of 4 up to 256, every
+ *   EfficientNet b0-b3 width), per pixel (k_dwconv) elsewhere; 0 = per pixel always.  Same y up to the sign of an
+ *   exact zero; the SE partial count per bev_dwconv_psum_blocks, which follows the knob.  1 / 2 (row runs up to 256
+ *   channels only, the wider layers on the LDS-tiled k_dwconv_t; last tree e891532) are rejected.  With the tile
+ *   gone, the channel counts that the runs cannot chunk and that have C / 4 even (C = 536 the smallest; none in
+ *   b0-b3) run k_dwconv at the defaults where they ran the tile (its 8-quad form at any size, its 4- / 2-quad forms
+ *   for outputs of at most 64 Ki pixels): y bit-identical (the same tap order), another SE partial count.
  * BEV_TUNE_CONV_X6_NT: 1 = non-temporal (streaming) activation loads in the split-arithmetic 1x1 / 3x3 convs with
  *   Co <= 64 tiles, 0 (default) = cached loads.  For the LAST reader of a large tensor: CNNEncoder sets it around its
  *   projection so the feature maps that conv writes stay in the Infinity Cache for the warp.  Same results.

@@ -46,14 +46,15 @@ def test_ctypes_signatures_cover_header(lib):
 
 def test_abi_version(lib):
     import bev_native
-    assert lib.bev_abi_version() == bev_native.ABI_VERSION
+    assert lib.bev_abi_version() == bev_native.ABI_VERSION == 17
 
 
 def test_abi_16_retired_the_fused_next_chain(lib):
-    """ABI 16 removed the pre-split chain that also ran the next block's conv1: the number is 16 and the library no
-    longer exports the entry point (its name is spelled in two halves so the tree stays free of it)."""
+    """ABI 16 removed the pre-split chain that also ran the next block's conv1: the library no longer exports the
+    entry point (its name is spelled in two halves so the tree stays free of it), at 16 or any later number
+    (test_abi_version pins the current one)."""
     gone = "bev_conv2d_chain_" + "next_x6_f32"
-    assert lib.bev_abi_version() == 16
+    assert lib.bev_abi_version() >= 16
     out = subprocess.check_output(["nm", "-D", "--defined-only", LIB], text=True)
     assert gone not in {line.split()[-1] for line in out.splitlines() if line.strip()}
     assert gone not in declared_symbols()
@@ -192,7 +193,7 @@ def test_tune_knobs_host_only(lib):
                             (nat.TUNE_WGRAD_MFMA, 0, 3), (nat.TUNE_CONV_X6_TILE, 2, 3),
                             (nat.TUNE_CONV_X6_KERNEL, 1, 3), (nat.TUNE_CONV_H16_KERNEL, 1, 4),
                             (nat.TUNE_CONV_PW_SMALL, 0, 5),
-                            (nat.TUNE_DW_RUN, 1, 4), (nat.TUNE_CONV_X6_NT, 1, 2),
+                            (nat.TUNE_DW_RUN, 0, 4), (nat.TUNE_CONV_X6_NT, 1, 2),
                             (nat.TUNE_STEM3_STAGE, 1, 3),
                             (nat.TUNE_WARP_SPAN, 50, 101), (nat.TUNE_WARP_TILE_BAND, 4, 65)):
         old = lib.bev_tune(knob, good)
@@ -207,6 +208,11 @@ def test_tune_knobs_host_only(lib):
     assert lib.bev_tune(nat.TUNE_WARP_TILE_BAND, 0) == 0
     # removed with ABI 14: the persistent kernel's knob (18, not reused)
     assert lib.bev_tune(18, 0) == -1
+    # removed with ABI 17: the values that selected retired depthwise kernels, and an alias
+    for knob, value in ((nat.TUNE_DW_RUN, 1), (nat.TUNE_DW_RUN, 2), (nat.TUNE_CONV_X6_KERNEL, 2)):
+        assert lib.bev_tune(knob, value) == -1
+    # ... and the default reads back unchanged
+    assert lib.bev_tune(nat.TUNE_DW_RUN, 3) == 3
 
 
 def test_no_environment_knobs_in_library():

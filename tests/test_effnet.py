@@ -120,7 +120,7 @@ def test_dwconv_and_se_vs_torch_fp32(case):
                                   (1, 192, 11, 19, 5, 2, 2), (1, 288, 9, 13, 5, 1, 2), (1, 384, 7, 9, 3, 1, 2)],
                          ids=lambda c: f"c{c[1]}_k{c[4]}s{c[5]}")
 def test_dwconv_row_runs_match_per_pixel(case):
-    """k_dwconv_r (BEV_TUNE_DW_RUN=1) == k_dwconv (=0): same taps in the same order, so y is identical up to the
+    """k_dwconv_r (BEV_TUNE_DW_RUN=3, the default) == k_dwconv (=0): same taps in the same order, so y is identical up to the
     sign of an exact zero (compared after + 0.0); the SE partials sum the same outputs in another grouping
     (per-image totals within fp32 tolerance)."""
     import bev_native as nat
@@ -130,7 +130,7 @@ def test_dwconv_row_runs_match_per_pixel(case):
     b = _rand((C,), 33, 0.1).to(DEV)
     with nat.tuned(DW_RUN=0):
         y0, p0 = nat.dwconv2d_nhwc(xd, wt, b, K, s, K // 2, act, want_psum=True)
-    for run in (1, 2, 3):  # 2: every kernel row's loads issued up front (3 x 3); 3: row runs for every width
+    for run in (3,):  # row runs for every width, every kernel row's loads issued up front for 3 x 3
         with nat.tuned(DW_RUN=run):
             y1, p1 = nat.dwconv2d_nhwc(xd, wt, b, K, s, K // 2, act, want_psum=True)
         assert torch.equal(y1 + 0.0, y0 + 0.0)

@@ -1,7 +1,7 @@
 """One case per kernel instantiation outside the conv sources that no other test launches (tools/kernel_coverage.py,
 profiles/r11a_kernel_coverage_after.txt): the fp16-store and SiLU + residual / mask-byte forms of bev_bn.hip, the
-scalar weight gradient k_wgrad of bev_train.hip, the LDS-tile and row-run depthwise kernels and every k_irdw of
-bev_effnet.hip, the register-staged fused warp k_warp_fuse and the span-staged channels-last k_warp_fuse_v2 of
+scalar weight gradient k_wgrad of bev_train.hip, the per-pixel depthwise kernel on a width the row runs do not take and
+every k_irdw of bev_effnet.hip, the register-staged fused warp k_warp_fuse and the span-staged channels-last k_warp_fuse_v2 of
 bev_warp.hip.  Each case forces its instance through the public wrappers, nat.lib() and nat.tuned(...), and its id
 names it (with the siblings of its family, so that a whole family is compared under one set of bounds).
 
@@ -16,16 +16,16 @@ oracle, bit for bit) -- never another kernel.  Bounds, all the project's:
  k_wgrad    1e-4 max|dW_ref| (float atomics change the summation order), against float64 autograd of F.conv2d and
             against the padded float4 / MFMA path (conv_wgrad_ex) within the same bar.
  depthwise  y within 1e-5 max|ref|; the SE partials summed over blocks within 1e-5 max(1, max|sums|) of the float64
-            channel sums of the reference; torch.equal(y + 0.0, y_default + 0.0) against BEV_TUNE_DW_RUN 3 (the header:
-            same y up to the sign of an exact zero).  k_irdw: the first two.
+            channel sums of the reference, their count bev_dwconv_psum_blocks'; torch.equal(y + 0.0, y_0 + 0.0) against
+            BEV_TUNE_DW_RUN 0 (the header: same y up to the sign of an exact zero).  k_irdw: the first two.
  warp       bit-identical to oracle.fused_stream; span staging also to the same launch with BEV_TUNE_WARP_SPAN 0 and
             to the NCHW output.
 
 Shapes: BatchNorm M = 2 x 13 x 17 = 442 rows (no multiple of BNQ_ROWS = 256 nor of BN_U x nph: the unrolled loop and
 the tail both run), C = 64 / 4 / 1024 (row-block kernels: 16 / 256 / 1 row phases) and 24 / 144 (flat grid-stride
 kernels), one flat case of M = 350001 rows (total4 > 8192 x 256: the grid-stride loop iterates twice); weight gradient
-N = 2 on 13 x 17 outputs (28 m-chunks of 16 rows, the last of 10); depthwise 11 x 19 outputs (two ragged 8 x 8 / 8 x 16
-tiles each way); k_irdw 19 output rows (two IR_RSEG = 16 segments) x tc + 3 columns (two strips, the last of 3), Cm = 96
+N = 2 on 13 x 17 outputs (28 m-chunks of 16 rows, the last of 10); depthwise 11 x 19 outputs (209 pixels: 27 workgroups
+of 8, the last of 1); k_irdw 19 output rows (two IR_RSEG = 16 segments) x tc + 3 columns (two strips, the last of 3), Cm = 96
 (two 48-channel groups); the warp on the small fixture geometries.
 """
 import os
@@ -305,7 +305,7 @@ def test_wgrad_scalar_kernel(case):
 
 
 # ======================================================================================================================
-# k_dwconv_t<K, S, DQ>, k_dwconv_r<3, 2, false> (bev_effnet.hip): BEV_TUNE_DW_RUN 1
+# k_dwconv<K> (bev_effnet.hip) at the defaults: channel counts that the row runs cannot chunk
 # ======================================================================================================================
 DW_HO, DW_WO = 11, 19
 
@@ -326,14 +326,14 @@ def _dw_op(C, K, S):
 def _dw_check(tag, C, K, S, nb):
     import bev_native as nat
     c = _dw_op(C, K, S)
+    assert nat.lib().bev_dwconv_psum_blocks(DW_HO, DW_WO, C, S) == nb, tag  # the count worked out in the case
     for act in (0, 2):
         ref = _act64(c["z"], act)
-        with nat.tuned(DW_RUN=1):
-            y, ps = nat.dwconv2d_nhwc(c["x"], c["wt"], c["b"], K, S, K // 2, act, want_psum=True)
-        with nat.tuned(DW_RUN=3):
+        y, ps = nat.dwconv2d_nhwc(c["x"], c["wt"], c["b"], K, S, K // 2, act, want_psum=True)
+        with nat.tuned(DW_RUN=0):
             y0, _ = nat.dwconv2d_nhwc(c["x"], c["wt"], c["b"], K, S, K // 2, act, want_psum=True)
         torch.cuda.synchronize()
-        assert y.shape == ref.shape and ps.shape == (2, nb, C), (tag, ps.shape)  # one SE partial per tile / run block
+        assert y.shape == ref.shape and ps.shape == (2, nb, C), (tag, ps.shape)  # one SE partial per workgroup
         _chk32(tag, f"y act {act}", y, ref, 1e-5)
         sums = ref.sum(dim=(1, 2))
         err = (ps.double().sum(1).cpu() - sums).abs().max().item()
@@ -341,24 +341,13 @@ def _dw_check(tag, C, K, S, nb):
         assert torch.equal(y + 0.0, y0 + 0.0), (tag, act)
 
 
-DW_T = [(K, S, dq) for K, S in ((3, 1), (3, 2), (5, 1), (5, 2)) for dq in (8, 4, 2)]
-
-
-@pytest.mark.parametrize("K,S,dq", DW_T, ids=[f"k_dwconv_t<{K},{S},{dq}>" for K, S, dq in DW_T])
-def test_dwconv_lds_tile_instances(K, S, dq):
-    """The LDS tile that BEV_TUNE_DW_RUN 0..2 selects: C = 64 / 48 / 24 -> 8- / 4- / 2-quad chunks, 11 x 19 outputs
-    (2 x 3 tiles of 8 x 8, 2 x 2 of 8 x 16, ragged both ways), act none and SiLU, SE partials."""
-    C = {8: 64, 4: 48, 2: 24}[dq]
-    tc = 16 if dq == 2 else 8
-    _dw_check(f"k_dwconv_t<{K},{S},{dq}>", C, K, S, -(-DW_HO // 8) * -(-DW_WO // tc))
-
-
-@pytest.mark.parametrize("instance", ["k_dwconv_r<3,2,false>"])
-def test_dwconv_row_run_k3_s2_loads_per_row(instance):
-    """k_dwconv_r<3, 2, false> (BEV_TUNE_DW_RUN 1: each kernel row's loads issued as it is used): C = 36, an odd quad
-    count that no LDS tile takes; 11 x 5 runs of 4 outputs, 28 runs per workgroup -> two SE partials."""
-    runs = DW_HO * -(-DW_WO // 4)
-    _dw_check(instance, 36, 3, 2, -(-runs // (256 // 9)))
+@pytest.mark.parametrize("K,S", [(3, 1), (5, 2)], ids=["k_dwconv<3>-c536-s1", "k_dwconv<5>-c536-s2"])
+def test_dwconv_unchunkable_width_runs_per_pixel(K, S):
+    """C = 536: 134 channel quads, which the row runs cannot split into equal chunks of at most 64 and whose even
+    count the LDS tile (last tree e891532) used to take at the defaults.  Now the per-pixel k_dwconv: 11 x 19
+    outputs, one pixel per step (256 // 134) -> 8 pixels per workgroup, 27 SE partials, the last workgroup ragged."""
+    ppb = 8 * (256 // (536 // 4))  # DW_STEPS pixel steps of 256 // (C / 4) pixels
+    _dw_check(f"k_dwconv<{K}> C 536 stride {S}", 536, K, S, -(-DW_HO * DW_WO // ppb))
 
 
 # ======================================================================================================================

@@ -27,7 +27,7 @@ VARIANTS = {
     "x6+x6chain12": ("bf16x6", set(), {1, 2}, False),
     "x6+split": ("bf16x6", set(), set(), True),
 }
-# stream-group variants of the default plan: "sg<G>"; split-kernel choice: "k<knob>" (BEV_TUNE_CONV_X6_KERNEL)
+# stream-group variants of the default plan: "sg<G>"; split-kernel choice: "k0" / "k1" (BEV_TUNE_CONV_X6_KERNEL)
 
 
 def main():

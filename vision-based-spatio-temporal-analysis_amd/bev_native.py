@@ -20,7 +20,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libbev_mi355x.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 BEV_ERR_ARGS = -1  # include/bev_mi355x.h: an argument the kernel cannot take
 
 FUSE_MODES = {"sum": 0, "mean": 1, "max": 2}

@@ -1083,7 +1083,7 @@ ConvX conv_x6_args(const float *x, const uint16_t *packed, const float *bias, co
 
 int g_x6_tile = 0;  // 0 automatic, 1 = 128 x 128, 2 = 128 x 64
 int g_x6_nt = 0;    // BEV_TUNE_CONV_X6_NT: 1 = non-temporal activation loads in the 32-deep kernels
-int g_x6_kernel = 0;  // 0 automatic, 1 = k_conv_x6 (16-deep K steps) everywhere, 2 = k_conv_x6b wherever it applies
+int g_x6_kernel = 0;  // 0 automatic (k_conv_x6b wherever it applies), 1 = k_conv_x6 (16-deep K steps) everywhere
 
 template <bool DUAL>
 int dispatch_x6(const ConvX &a0, hipStream_t st) {
@@ -1132,19 +1132,15 @@ constexpr int NE = 3 * PR * PC;
 constexpr int PER_T = (NE + NTHR - 1) / NTHR;
 constexpr int NS = 10;            // 16-deep k slices (147 -> 160)
 constexpr int WB = 2 * NS * 3 * 512;  // bf16 of the panel's first two 32-column blocks
-// STEM6_PRESPLIT 1: the patch is split into h / m / l once, when it is written to LDS (a dword plane of (h, m) pairs
-// and a 16-bit plane of l): each input value serves ~12 (tap, pixel) products, so splitting per use (0: fp32 patch,
-// split3 on every A element) costs ~12x the conversions.
+// The patch is split into h / m / l once, when it is written to LDS (a dword plane of (h, m) pairs and a 16-bit plane
+// of l): each input value serves ~12 (tap, pixel) products, so splitting per use (an fp32 patch with split3 on every
+// A element: the STEM6_PRESPLIT 0 arm, last in e891532) costs ~12x the conversions; it measured the same time.
 // LDS float offset of panel k (k = (ky * 7 + kx) * 3 + ci) relative to (output row 0, output column 0) of the patch;
 // the padding k >= 147 reads tap 0 (its weight is zero)
 __host__ __device__ constexpr int koff(int k) {
     return k >= 147 ? 0 : (k % 3) * CP + (k / 21) * RP + (((k / 3) % 7) & 1) * PP + (((k / 3) % 7) >> 1);
 }
 }  // namespace stem6
-
-#ifndef STEM6_PRESPLIT
-#define STEM6_PRESPLIT 1
-#endif
 
 struct StemX6Args {
     const float *__restrict__ x;
@@ -1187,15 +1183,12 @@ __device__ __forceinline__ void stem6_put(float *pl, int tid, const float (&pv)[
             const int cr = e / PC, c = e - cr * PC;
             const int ci = cr / PR, r = cr - ci * PR;
             const int o = ci * CP + r * RP + (c & 1) * PP + (c >> 1);
-            if (STEM6_PRESPLIT) {  // pl = the (h, m) dword plane, followed by the l plane (PATCH bf16)
-                __bf16 hh, mm, ll;
-                split3(pv[i], hh, mm, ll);
-                reinterpret_cast<unsigned *>(pl)[o] = (unsigned)__builtin_bit_cast(unsigned short, hh) |
-                                                      ((unsigned)__builtin_bit_cast(unsigned short, mm) << 16);
-                reinterpret_cast<__bf16 *>(pl + PATCH)[o] = ll;
-            } else {
-                pl[o] = pv[i];
-            }
+            // pl = the (h, m) dword plane, followed by the l plane (PATCH bf16)
+            __bf16 hh, mm, ll;
+            split3(pv[i], hh, mm, ll);
+            reinterpret_cast<unsigned *>(pl)[o] = (unsigned)__builtin_bit_cast(unsigned short, hh) |
+                                                  ((unsigned)__builtin_bit_cast(unsigned short, mm) << 16);
+            reinterpret_cast<__bf16 *>(pl + PATCH)[o] = ll;
         }
     }
 }
@@ -1219,7 +1212,7 @@ __device__ __forceinline__ float pool_mx(float m, float v) { return max_nan(m, v
 template <bool POOL>
 __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
     using namespace stem6;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[WB * 2 + PATCH * (STEM6_PRESPLIT ? 6 : 4)];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[WB * 2 + PATCH * 6];
     __bf16 *wl = (__bf16 *)lds_raw;
     float *pl = (float *)(lds_raw + WB * 2);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
@@ -1232,7 +1225,7 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
     __syncthreads();
 
     const float *P = pl + wave * 2 * RP + r32;  // output row `wave`, column r32 (+ 32 for the second M tile)
-    const __bf16 *PL = reinterpret_cast<const __bf16 *>(pl + PATCH) + wave * 2 * RP + r32;  // its l plane (PRESPLIT)
+    const __bf16 *PL = reinterpret_cast<const __bf16 *>(pl + PATCH) + wave * 2 * RP + r32;  // its l plane
     const float b0 = (r32 < a.Co) ? a.bias[r32] : 0.0f;
     const float b1 = (32 + r32 < a.Co) ? a.bias[32 + r32] : 0.0f;
     for (; t < a.ntiles; t += gridDim.x) {
@@ -1262,18 +1255,10 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                 for (int e = 0; e < 8; ++e) {
                     const int o0 = koff(16 * sl + e), o1 = koff(16 * sl + 8 + e);
                     const int o = 32 * mt + (hv ? o1 : o0);
-                    if (STEM6_PRESPLIT) {
-                        const unsigned hm = reinterpret_cast<const unsigned *>(P)[o];
-                        fa[0][e] = __builtin_bit_cast(__bf16, (unsigned short)(hm & 0xffffu));
-                        fa[1][e] = __builtin_bit_cast(__bf16, (unsigned short)(hm >> 16));
-                        fa[2][e] = PL[o];
-                    } else {
-                        __bf16 hh, mm, ll;
-                        split3(P[o], hh, mm, ll);
-                        fa[0][e] = hh;
-                        fa[1][e] = mm;
-                        fa[2][e] = ll;
-                    }
+                    const unsigned hm = reinterpret_cast<const unsigned *>(P)[o];
+                    fa[0][e] = __builtin_bit_cast(__bf16, (unsigned short)(hm & 0xffffu));
+                    fa[1][e] = __builtin_bit_cast(__bf16, (unsigned short)(hm >> 16));
+                    fa[2][e] = PL[o];
                 }
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -1469,7 +1454,7 @@ __global__ __launch_bounds__(256) void k_stem_pool_seams(float *__restrict__ y, 
 namespace bev {
 int conv_x6_tune(int knob, int value) {
     int *slot = knob == BEV_TUNE_CONV_X6_TILE ? &g_x6_tile : knob == BEV_TUNE_CONV_X6_NT ? &g_x6_nt : &g_x6_kernel;
-    if (value < 0 || value > 2 || (knob == BEV_TUNE_CONV_X6_NT && value > 1)) return BEV_ERR_ARGS;
+    if (value < 0 || value > (knob == BEV_TUNE_CONV_X6_TILE ? 2 : 1)) return BEV_ERR_ARGS;
     const int old = *slot;
     *slot = value;
     return old;

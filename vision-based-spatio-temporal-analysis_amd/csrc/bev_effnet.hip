@@ -112,20 +112,23 @@ __global__ __launch_bounds__(DW_NT) void k_dwconv(const float *__restrict__ x, i
 }
 
 
-// Row-run depthwise K x K for narrow channel counts (C / 4 <= 64 quads, where the LDS tile loses: B3's 540 x 960 C 24 /
-// C 40 and 270 x 480 C 144 stride-2 layers).  A thread owns one channel quad of R consecutive outputs of one row;
+// Row-run depthwise K x K, stride 1 / 2, for every channel count whose quads split into equal chunks of at most 64
+// (dw_run_ch4: all of EfficientNet b0-b3).  A thread owns one channel quad of R consecutive outputs of one row;
 // for each kernel row it loads the (R - 1) * S + K input pixels the run needs once into registers and applies them
 // to all R outputs, so every input quad is fetched once per kernel row and run instead of K times per output (the
 // per-pixel kernel's K * K tap loads per output were bound by the L1 / address rate, 0.28 of HBM on those layers).
 // The C / 4 lanes of a run read each pixel as one contiguous segment.  Per output the taps are applied in
 // k_dwconv's order (ky-major, kx-minor; out-of-range rows skipped, out-of-range columns read as 0, so y matches
-// k_dwconv up to the sign of an exact zero); SE partials per workgroup in a fixed order.
-// BEV_TUNE_DW_RUN: 0 keeps these layers on k_dwconv; 1 row runs; 2 row runs with every kernel row's loads issued up
-// front for 3 x 3 (more VGPRs, fewer exposed latencies); 3 (default) = 2 also for the widths the LDS tile took.
+// k_dwconv up to the sign of an exact zero); SE partials per workgroup in a fixed order.  For 3 x 3 every kernel row's
+// loads are issued up front (UP: more VGPRs, fewer exposed latencies).
+// BEV_TUNE_DW_RUN: 3 (default) = row runs wherever they apply; 0 keeps every layer on k_dwconv, which also takes the
+// other strides and the channel counts the runs cannot chunk.  Values 1 / 2 (runs for C / 4 <= 64 only, without / with
+// UP, the wider layers on the LDS-tiled k_dwconv_t) and that kernel were last in e891532.
 // r03i (EfficientNet-B3 bench, profiles/r03i_dw_run_ab.txt): per-pixel -> runs -> up front: 540 x 960 C 24
 // 623 -> 421 -> 401 us, C 40 1031 -> 701 -> 671, 270 x 480 C 144 s2 1271 -> 1039 -> 980 (120.1 -> 126.8 frames/s);
 // LDS tile -> runs: 270 x 480 C 192 k3 819 -> 706, 135 x 240 C 288 k5 645 -> 439, C 192 k5 s2 1105 -> 522 us
-// (127.1 -> 136.0 frames/s).
+// (127.1 -> 136.0 frames/s).  The LDS tile itself had beaten k_dwconv on the widths it took (r02r micro, 7 x 1080p B3
+// shapes: C 192 k3 659 -> 435 us, 192 k5 s2 735 -> 572, 288 k5 927 -> 340) and lost on the narrow ones.
 int g_dw_run = 3;
 template <int S> constexpr int dw_run_len() { return S == 1 ? 8 : 4; }
 inline int dw_run_ch4(int C) {
@@ -135,12 +138,13 @@ inline int dw_run_ch4(int C) {
     return 0;
 }
 
-template <int K, int S, bool UP>
+template <int K, int S>
 __global__ __launch_bounds__(DW_NT) void k_dwconv_r(const float *__restrict__ x, int H, int W, int C,
                                                     const float *__restrict__ wt, const float *__restrict__ bias,
                                                     int pad, int act, float *__restrict__ y, int Ho, int Wo,
                                                     float *__restrict__ psum, int nb, int CH4) {
     constexpr int R = dw_run_len<S>(), IC = (R - 1) * S + K;
+    constexpr bool UP = K == 3;
     __shared__ float4 red[DW_NT];
     const int PB = DW_NT / CH4;  // runs per workgroup; CH4 channel quads per workgroup (blockIdx.z chunks)
     const int tid = threadIdx.x, pl = tid / CH4, q = blockIdx.z * CH4 + (tid - pl * CH4);
@@ -232,116 +236,6 @@ __global__ __launch_bounds__(DW_NT) void k_dwconv_r(const float *__restrict__ x,
         }
         *(float4 *)(psum + ((int64_t)n * nb + blk) * C + q * 4) = s;
     }
-}
-
-// LDS-tiled depthwise conv: a workgroup owns an 8-row output-pixel tile x DQ channel quads (DQ = 8: 32 channels =
-// one 128-B line of every pixel, 8 columns; DQ = 4: 8 columns; DQ = 2: 16 columns).  The tile's input patch is
-// staged in LDS once (pixel stride DQ + 1 quads: conflict-free ds_read_b128 for stride 1 and 2), so the K*K taps
-// of every output read LDS instead of re-streaming whole pixels from L2 (the per-pixel kernel's K=5 working set
-// over 1-KB pixels exceeds the 32-KB L1).  Per output the taps are applied in the same order as k_dwconv
-// (ky-major, kx-minor, out-of-range taps skipped), so y is bit-identical to it; the SE partial sums are per tile
-// (fixed order), so their rounding differs from k_dwconv's partition.
-constexpr int DT_R = 8;  // output tile rows
-__host__ __device__ constexpr int dt_cols(int dq) { return dq == 2 ? 16 : 8; }
-
-inline int dw_dq(int C) {
-    const int C4 = C / 4;
-    return C4 % 8 == 0 ? 8 : C4 % 4 == 0 ? 4 : C4 % 2 == 0 ? 2 : 0;
-}
-inline int dt_tiles(int Ho, int Wo, int dq) {
-    return ((Ho + DT_R - 1) / DT_R) * ((Wo + dt_cols(dq) - 1) / dt_cols(dq));
-}
-
-template <int K, int S, int DQ>
-__global__ __launch_bounds__(256) void k_dwconv_t(const float *__restrict__ x, int H, int W, int C,
-                                                  const float *__restrict__ wt, const float *__restrict__ bias,
-                                                  int pad, int act, float *__restrict__ y, int Ho, int Wo,
-                                                  float *__restrict__ psum, int nb) {
-    constexpr int TC = dt_cols(DQ), NPL = 256 / DQ, OPT = DT_R * TC / NPL, RS = DT_R / OPT;
-    constexpr int PRR = (DT_R - 1) * S + K, PRC = (TC - 1) * S + K, PS = DQ + 1;
-    __shared__ float4 patch[PRR * PRC * PS];
-    __shared__ float4 red[256];
-    const int tid = threadIdx.x, q = tid % DQ, pl = tid / DQ, c = pl % TC, r = pl / TC;  // r < RS
-    const int n = blockIdx.y, tile = blockIdx.x, cq = blockIdx.z * DQ + q;
-    const int ntx = (Wo + TC - 1) / TC;
-    const int oy0 = (tile / ntx) * DT_R, ox0 = (tile % ntx) * TC;
-    const int iy0 = oy0 * S - pad, ix0 = ox0 * S - pad;
-    const float *xn = x + (int64_t)n * H * W * C + blockIdx.z * DQ * 4;
-    for (int e = tid; e < PRR * PRC * DQ; e += 256) {
-        const int qq = e % DQ, pp = e / DQ, pr = pp / PRC, pc = pp - pr * PRC;
-        const int iy = iy0 + pr, ix = ix0 + pc;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-            v = *(const float4 *)(xn + ((int64_t)iy * W + ix) * C + qq * 4);
-        patch[(pr * PRC + pc) * PS + qq] = v;
-    }
-    __syncthreads();
-    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    {
-        float4 w[K * K];
-#pragma unroll
-        for (int t = 0; t < K * K; ++t) w[t] = *(const float4 *)(wt + (int64_t)t * C + cq * 4);
-        const float4 b = *(const float4 *)(bias + cq * 4);
-        const int ox = ox0 + c;
-#pragma unroll
-        for (int h = 0; h < OPT; ++h) {
-            const int rr = r + RS * h, oy = oy0 + rr;
-            if (oy >= Ho || ox >= Wo) continue;
-            float4 acc = b;
-#pragma unroll
-            for (int ky = 0; ky < K; ++ky) {
-                const int iy = iy0 + rr * S + ky;
-                if (iy < 0 || iy >= H) continue;
-#pragma unroll
-                for (int kx = 0; kx < K; ++kx) {
-                    const int ix = ix0 + c * S + kx;
-                    if (ix < 0 || ix >= W) continue;
-                    const float4 v = patch[((rr * S + ky) * PRC + c * S + kx) * PS + q];
-                    const float4 ww = w[ky * K + kx];
-                    acc.x = __builtin_fmaf(v.x, ww.x, acc.x);
-                    acc.y = __builtin_fmaf(v.y, ww.y, acc.y);
-                    acc.z = __builtin_fmaf(v.z, ww.z, acc.z);
-                    acc.w = __builtin_fmaf(v.w, ww.w, acc.w);
-                }
-            }
-            acc.x = act_f(acc.x, act);
-            acc.y = act_f(acc.y, act);
-            acc.z = act_f(acc.z, act);
-            acc.w = act_f(acc.w, act);
-            *(float4 *)(y + (((int64_t)n * Ho + oy) * Wo + ox) * C + cq * 4) = acc;
-            s4.x += acc.x;
-            s4.y += acc.y;
-            s4.z += acc.z;
-            s4.w += acc.w;
-        }
-    }
-    if (psum == nullptr) return;
-    red[tid] = s4;
-    __syncthreads();
-    if (pl == 0) {  // fixed order over the pixel lanes: deterministic partial
-        for (int l = 1; l < NPL; ++l) {
-            const float4 t = red[l * DQ + q];
-            s4.x += t.x;
-            s4.y += t.y;
-            s4.z += t.z;
-            s4.w += t.w;
-        }
-        *(float4 *)(psum + ((int64_t)n * nb + tile) * C + cq * 4) = s4;
-    }
-}
-
-template <int K, int S>
-void launch_dwconv_t(int dq, dim3 grid, hipStream_t st, const float *x, int H, int W, int C, const float *wt,
-                     const float *bias, int pad, int act, float *y, int Ho, int Wo, float *psum, int nb) {
-    if (dq == 8)
-        hipLaunchKernelGGL((k_dwconv_t<K, S, 8>), grid, dim3(256), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
-                           psum, nb);
-    else if (dq == 4)
-        hipLaunchKernelGGL((k_dwconv_t<K, S, 4>), grid, dim3(256), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
-                           psum, nb);
-    else
-        hipLaunchKernelGGL((k_dwconv_t<K, S, 2>), grid, dim3(256), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
-                           psum, nb);
 }
 
 constexpr int SE_NT = 1024;  // threads of the SE gate workgroup (one per image)
@@ -743,27 +637,10 @@ inline int last() {
     return e == hipSuccess ? 0 : (int)e;
 }
 
-}  // namespace
-
-extern "C" {
-
-// Which kernel: k_dwconv_t with 8-quad (32-channel) chunks whenever C % 32 == 0 -- r02r micro (7 x 1080p B3 shapes):
-// C 192 k3 659 -> 435 us, 192 k5 s2 735 -> 572, 288 k5 927 -> 340 -- and with 4- / 2-quad chunks only for outputs of
-// at most 64 Ki pixels per image: r02r, B0's k5 layers at 135 x 240 (C 144 / 240) gain (B0 training step 44.6 ->
-// 42.9 ms) while B3's 540 x 960 C 40 and 270 x 480 C 144 layers lose badly (572 -> 1360, 665 -> 1042 us: 32- / 64-B
-// pixel segments per patch load).  The tiled kernel takes stride 1 or 2; other strides run the per-pixel kernel.
-// The choice depends on (Ho, Wo, C, stride) only, so the SE partial count below always matches the kernel that runs.
-inline int dw_tiled_dq(int Ho, int Wo, int C, int stride) {
-    const int dq = dw_dq(C);
-    if (stride != 1 && stride != 2) return 0;
-    if (g_dw_run == 3 && dw_run_ch4(C) > 0) return 0;  // row runs for every width
-    return (dq == 8 || (dq > 0 && (int64_t)Ho * Wo <= 65536)) ? dq : 0;
-}
-
-// k_dwconv_r: stride 1 / 2; channel quads per workgroup = C / 4 split into equal chunks of at most 64
-inline bool dw_use_run(int stride, int C) {
-    return g_dw_run && (stride == 1 || stride == 2) && (C / 4 <= 64 || (g_dw_run == 3 && dw_run_ch4(C) > 0));
-}
+// Which depthwise kernel: the row runs for stride 1 / 2 wherever the channel quads split into equal chunks of at most
+// 64, else the per-pixel k_dwconv.  The choice depends on (C, stride) and BEV_TUNE_DW_RUN only, and the SE partial
+// count (bev_dwconv_psum_blocks) and the launch both take it from here.
+inline bool dw_use_run(int stride, int C) { return g_dw_run && (stride == 1 || stride == 2) && dw_run_ch4(C) > 0; }
 inline int dw_run_blocks(int Ho, int Wo, int C, int stride) {
     const int R = stride == 1 ? dw_run_len<1>() : dw_run_len<2>(), PB = DW_NT / dw_run_ch4(C);
     return (int)(((int64_t)Ho * ((Wo + R - 1) / R) + PB - 1) / PB);
@@ -779,7 +656,7 @@ int stem3_tune(int value) {
     return old;
 }
 int dw_tune(int value) {
-    if (value < 0 || value > 3) return BEV_ERR_ARGS;
+    if (value != 0 && value != 3) return BEV_ERR_ARGS;  // 1 / 2: retired arms
     const int old = g_dw_run;
     g_dw_run = value;
     return old;
@@ -790,8 +667,6 @@ extern "C" {
 
 int bev_dwconv_psum_blocks(int Ho, int Wo, int C, int stride) {
     if (Ho <= 0 || Wo <= 0 || C <= 0 || C % 4 != 0 || stride <= 0) return BEV_ERR_ARGS;
-    const int dq = dw_tiled_dq(Ho, Wo, C, stride);
-    if (dq) return dt_tiles(Ho, Wo, dq);  // one SE partial per output tile
     if (dw_use_run(stride, C)) return dw_run_blocks(Ho, Wo, C, stride);
     const int ppb = dw_ppb(C);
     return (int)(((int64_t)Ho * Wo + ppb - 1) / ppb);
@@ -809,51 +684,32 @@ int bev_dwconv2d_f32(const float *x, int N, int H, int W, int C, const float *wt
         return BEV_ERR_ARGS;
     if (N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int dq = dw_tiled_dq(Ho, Wo, C, stride);
-    if (!dq && dw_use_run(stride, C)) {
-        const int nb = dw_run_blocks(Ho, Wo, C, stride), CH4 = dw_run_ch4(C);
+    const int nb = bev_dwconv_psum_blocks(Ho, Wo, C, stride);
+    if (dw_use_run(stride, C)) {
+        const int CH4 = dw_run_ch4(C);
         dim3 grid(nb, N, C / 4 / CH4);
-        if (g_dw_run >= 2 && K == 3) {
-            if (stride == 1)
-                hipLaunchKernelGGL((k_dwconv_r<3, 1, true>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y,
-                                   Ho, Wo, psum, nb, CH4);
-            else
-                hipLaunchKernelGGL((k_dwconv_r<3, 2, true>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y,
-                                   Ho, Wo, psum, nb, CH4);
-            return last();
-        }
         if (K == 3 && stride == 1)
-            hipLaunchKernelGGL((k_dwconv_r<3, 1, false>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
+            hipLaunchKernelGGL((k_dwconv_r<3, 1>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
                                psum, nb, CH4);
         else if (K == 3)
-            hipLaunchKernelGGL((k_dwconv_r<3, 2, false>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
+            hipLaunchKernelGGL((k_dwconv_r<3, 2>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
                                psum, nb, CH4);
         else if (stride == 1)
-            hipLaunchKernelGGL((k_dwconv_r<5, 1, false>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
+            hipLaunchKernelGGL((k_dwconv_r<5, 1>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
                                psum, nb, CH4);
         else
-            hipLaunchKernelGGL((k_dwconv_r<5, 2, false>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
+            hipLaunchKernelGGL((k_dwconv_r<5, 2>), grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo,
                                psum, nb, CH4);
         return last();
     }
-    if (!dq) {
-        const int nb = bev_dwconv_psum_blocks(Ho, Wo, C, stride), ppb = dw_ppb(C);
-        const int C4 = C / 4, CH4 = dw_ch4(C);
-        dim3 grid(nb, N, (C4 + CH4 - 1) / CH4);
-        if (K == 3)
-            hipLaunchKernelGGL(k_dwconv<3>, grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, stride, pad, act, y, Ho,
-                               Wo, psum, nb, ppb);
-        else
-            hipLaunchKernelGGL(k_dwconv<5>, grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, stride, pad, act, y, Ho,
-                               Wo, psum, nb, ppb);
-        return last();
-    }
-    const int nb = dt_tiles(Ho, Wo, dq);
-    dim3 grid(nb, N, C / 4 / dq);
-    if (K == 3 && stride == 1) launch_dwconv_t<3, 1>(dq, grid, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo, psum, nb);
-    else if (K == 3) launch_dwconv_t<3, 2>(dq, grid, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo, psum, nb);
-    else if (stride == 1) launch_dwconv_t<5, 1>(dq, grid, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo, psum, nb);
-    else launch_dwconv_t<5, 2>(dq, grid, st, x, H, W, C, wt, bias, pad, act, y, Ho, Wo, psum, nb);
+    const int ppb = dw_ppb(C), C4 = C / 4, CH4 = dw_ch4(C);
+    dim3 grid(nb, N, (C4 + CH4 - 1) / CH4);
+    if (K == 3)
+        hipLaunchKernelGGL(k_dwconv<3>, grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, stride, pad, act, y, Ho, Wo,
+                           psum, nb, ppb);
+    else
+        hipLaunchKernelGGL(k_dwconv<5>, grid, dim3(DW_NT), 0, st, x, H, W, C, wt, bias, stride, pad, act, y, Ho, Wo,
+                           psum, nb, ppb);
     return last();
 }
 
