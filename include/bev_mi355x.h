@@ -841,6 +841,32 @@ int bev_decode_nms_large_f32(const int32_t *cand_idx, const float *cand_score, c
 int bev_image_normalize_u8_f32(const uint8_t *src, int N, int H, int W, const float *mean, const float *std,
                                float *out, void *stream);
 
+/* Camera-image ingest from native-size frames: T.Resize((H, W)) (data/transforms.py:13, applied per image in
+ * data/wildtrack_loader.py:368-374; torchvision's PIL path, img.resize((W, H), Image.BILINEAR)) + T.ToTensor +
+ * T.Normalize (transforms.py:17-18) in one launch.  Pillow's 8-bit resize is integer arithmetic on 22-bit
+ * fixed-point coefficients -- horizontal pass to a uint8 intermediate (only if Ws != W), then vertical pass (only if
+ * Hs != H), each clip8((2^21 + sum src * k) >> 22) -- so the output is bit-identical to
+ * Normalize(ToTensor(Resize((H, W))(img))).  Added under ABI 17 (new entries only; the number does not move).
+ *
+ * Accepted geometries: every size in 1 .. 2^24, and per axis in_size <= 17 * out_size (any upscale; a downscale of
+ * up to 17x, which is ksize <= 35 taps); bev_image_resize_plan_bytes is 0 and the other two return BEV_ERR_ARGS for
+ * anything else.
+ *
+ * host: bytes of the coefficient blob of a geometry, 0 for one the kernel does not take.  The blob is int32:
+ * x bounds [W][2] = (first source column, taps), x coefficients [W][ksize_x] (zero past the taps), y bounds [H][2],
+ * y coefficients [H][ksize_y]; ksize = 2 * ceil(max(in_size / out_size, 1)) + 1, a function of the sizes alone. */
+int64_t bev_image_resize_plan_bytes(int Hs, int Ws, int H, int W);
+/* host, no HIP call: fills host_buf (4-B aligned, bytes == bev_image_resize_plan_bytes) with Pillow's coefficients
+ * (precompute_coeffs + normalize_coeffs_8bpc, in double).  The caller copies it to the device once per geometry. */
+int bev_image_resize_plan(int Hs, int Ws, int H, int W, void *host_buf, int64_t bytes);
+/* device: src [N][Hs][Ws][3] uint8 RGB, any byte alignment -> out [N][3][H][W] fp32 (4-B aligned; float4
+ * non-temporal stores when W % 4 == 0 and out is 16-B aligned).  plan_dev: the blob on the device (4-B aligned);
+ * mean, std: host float[3].  Allocates nothing and synchronises nothing (capturable).  Arguments are checked on the
+ * host before any launch: BEV_ERR_ARGS for a null pointer, N < 0, a non-positive size or a refused geometry; N == 0
+ * is a no-op.  (Hs, Ws) == (H, W) runs bev_image_normalize_u8_f32's kernels.  Element offsets are 64-bit. */
+int bev_image_resize_normalize_u8_f32(const uint8_t *src, int N, int Hs, int Ws, const void *plan_dev, int H, int W,
+                                      const float *mean, const float *std, float *out, void *stream);
+
 /* BEVNet head operand (model_wrapper.py:69-75 -- proj bias add, pos-enc concat; the reference's torch.cat of the
  * projection [B,P,Hb,Wb] and pos_enc [2,Hb,Wb]): x [B][Hb][Wb][cp] channels-last = (s + bias, pos, 0...) per cell, s the
  * fused warp-sum of the projected views [B][P][Hb][Wb]; cp >= P + 2 (the head's padded input width), P <= 512.  The

@@ -132,6 +132,9 @@ SIGNATURES = {
     "bev_groupnorm_fwd_f32": (_i, [_vp, _i, _i64, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bev_groupnorm_apply_f32": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i, _vp, _vp]),
     "bev_image_normalize_u8_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bev_image_resize_plan_bytes": (_i64, [_i, _i, _i, _i]),
+    "bev_image_resize_plan": (_i, [_i, _i, _i, _i, _vp, _i64]),
+    "bev_image_resize_normalize_u8_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "bev_groupnorm_bwd_f32": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "bev_conv_packed_size_h16": (_i64, [_i, _i, _i, _i]),
     "bev_conv_pack_weights_h16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
@@ -2051,4 +2054,73 @@ def image_normalize_u8(src: torch.Tensor, mean, std, out: torch.Tensor = None) -
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
     _check(lib().bev_image_normalize_u8_f32(_ptr(src), N, H, W, m, s, _ptr(out), _stream(src)),
            "bev_image_normalize_u8_f32")
+    return out
+
+
+def _resize_plan_blob(Hs: int, Ws: int, H: int, W: int):
+    """The coefficient blob of one geometry as a host int32 array (bev_image_resize_plan)."""
+    import numpy as np
+    L = lib()
+    nbytes = int(L.bev_image_resize_plan_bytes(Hs, Ws, H, W))
+    if nbytes <= 0:
+        raise ValueError(f"image resize {Hs}x{Ws} -> {H}x{W}: sizes must be positive and at most 2^24, and a downscale "
+                         f"at most 17x per axis")
+    blob = np.empty(nbytes // 4, dtype=np.int32)
+    _check(L.bev_image_resize_plan(Hs, Ws, H, W, ctypes.c_void_p(blob.ctypes.data), nbytes), "bev_image_resize_plan")
+    return blob
+
+
+def _ksize(in_size: int, out_size: int) -> int:  # include/bev_mi355x.h: a function of the two sizes alone
+    import math
+    return 2 * math.ceil(max(in_size / out_size, 1.0)) + 1  # sizes <= 2^24 are exact in the C side's float
+
+
+def image_resize_plan(in_hw, out_hw) -> dict:
+    """Pillow's BILINEAR resize tables for (Hs, Ws) -> (H, W), as the device kernel reads them (no GPU needed):
+    {"x": {"ksize", "bounds" [W, 2] int32 (first source column, taps), "coeffs" [W, ksize] int32 (22-bit fixed
+    point, zero past the taps)}, "y": the same for rows}.  One pass is clip8((2^21 + sum src * k) >> 22) per
+    channel, horizontal first (uint8 intermediate), then vertical: what another host needs to check its own port."""
+    (Hs, Ws), (H, W) = (int(v) for v in in_hw), (int(v) for v in out_hw)
+    blob = _resize_plan_blob(Hs, Ws, H, W)
+    ksx, ksy = _ksize(Ws, W), _ksize(Hs, H)
+    assert blob.size == W * (2 + ksx) + H * (2 + ksy), (blob.size, ksx, ksy)
+    xb, xk, yb, yk = (blob[a:b] for a, b in ((0, 2 * W), (2 * W, W * (2 + ksx)), (W * (2 + ksx), W * (2 + ksx) + 2 * H),
+                                             (W * (2 + ksx) + 2 * H, blob.size)))
+    return {"x": {"ksize": ksx, "bounds": xb.reshape(W, 2).copy(), "coeffs": xk.reshape(W, ksx).copy()},
+            "y": {"ksize": ksy, "bounds": yb.reshape(H, 2).copy(), "coeffs": yk.reshape(H, ksy).copy()}}
+
+
+_RESIZE_PLANS = {}  # (device index, Hs, Ws, H, W) -> the coefficient blob on that device
+
+
+def _resize_plan_dev(device: torch.device, Hs: int, Ws: int, H: int, W: int) -> torch.Tensor:
+    key = (device.index if device.index is not None else torch.cuda.current_device(), Hs, Ws, H, W)
+    plan = _RESIZE_PLANS.get(key)
+    if plan is None:
+        plan = torch.from_numpy(_resize_plan_blob(Hs, Ws, H, W)).to(device)
+        _RESIZE_PLANS[key] = plan
+    return plan
+
+
+def image_resize_normalize_u8(src: torch.Tensor, out_hw, mean, std, out: torch.Tensor = None) -> torch.Tensor:
+    """[N, Hs, Ws, 3] uint8 RGB on the GPU -> [N, 3, H, W] fp32: PIL's BILINEAR Resize((H, W)) + ToTensor + Normalize in
+    one launch (bev_image_resize_normalize_u8_f32), bit-identical to the CPU transforms.  The coefficient tables of a
+    geometry are built on the host once and kept on the device."""
+    if not src.is_cuda:
+        raise HipError("image_resize_normalize_u8 needs a ROCm device tensor (got a CPU tensor); no CPU fallback")
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"image_resize_normalize_u8 expects [N, Hs, Ws, 3] uint8, got {tuple(src.shape)} {src.dtype}")
+    H, W = (int(v) for v in out_hw)
+    src = src.contiguous()
+    N, Hs, Ws, _ = src.shape
+    if out is None:
+        out = torch.empty(N, 3, H, W, device=src.device, dtype=torch.float32)
+    elif (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, 3, H, W)
+          or not out.is_contiguous()):
+        raise ValueError(f"image_resize_normalize_u8: out must be a contiguous [{N}, 3, {H}, {W}] fp32 device tensor")
+    plan = _resize_plan_dev(src.device, Hs, Ws, H, W)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    _check(lib().bev_image_resize_normalize_u8_f32(_ptr(src), N, Hs, Ws, _ptr(plan), H, W, m, s, _ptr(out),
+                                                   _stream(src)), "bev_image_resize_normalize_u8_f32")
     return out

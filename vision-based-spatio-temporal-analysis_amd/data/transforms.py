@@ -18,6 +18,18 @@ The last two steps are split off by `build_transforms(..., normalize=False)`: th
 stops at an 8-bit HWC array, the batch crosses PCIe at a quarter of the fp32 bytes and
 `normalize_on_device` (HIP kernel `bev_image_normalize_u8_f32`) produces the bit-identical fp32
 [N, 3, H, W] input on the GPU.
+
+`resize_normalize_on_device` (HIP kernel `bev_image_resize_normalize_u8_f32`) moves `Resize` to the
+device as well: native-size uint8 frames in, the [N, 3, H, W] fp32 input out, in one launch and
+bit-identical to `Normalize(ToTensor(Resize(img)))` (PIL's resize is integer arithmetic on
+fixed-point coefficients, which the kernel repeats).  Its host side is
+`build_transforms(img_size, normalize=False, resize=False)`: the deterministic ingest, which only
+decodes to uint8 HWC -- no `Resize`, and no `ColorJitter` either, drawing nothing from the RNG.
+The jitter cannot stay: in the reference it sits between `Resize` and `ToTensor`, so jittering the
+native-size frame before a device resize would produce a different image from the reference's
+(the enhancements are not linear in the pixels, and the resize rounds to uint8 before them).  The
+reference jitters at inference too (p = 0.5, the same transform for every split: a quirk), so this
+mode reproduces exactly the draws on which `RandomApply` skips the jitter.
 """
 from __future__ import annotations
 
@@ -31,7 +43,7 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 __all__ = ["build_transforms", "Compose", "Resize", "RandomApply", "ColorJitter", "ToTensor", "Normalize",
-           "ToUint8HWC", "normalize_on_device", "IMAGENET_MEAN", "IMAGENET_STD"]
+           "ToUint8HWC", "normalize_on_device", "resize_normalize_on_device", "IMAGENET_MEAN", "IMAGENET_STD"]
 
 
 class Compose:
@@ -146,8 +158,14 @@ class Normalize:
         return t.sub(self.mean).div(self.std)
 
 
-def build_transforms(img_size=(256, 256), normalize: bool = True) -> Compose:
-    """The reference pipeline (transforms.py:12-19).  normalize=False stops at uint8 HWC (see module doc)."""
+def build_transforms(img_size=(256, 256), normalize: bool = True, resize: bool = True) -> Compose:
+    """The reference pipeline (transforms.py:12-19).  normalize=False stops at uint8 HWC; resize=False (needs
+    normalize=False) only decodes to uint8 HWC at the frame's own size, without jitter (see module doc)."""
+    if not resize:
+        if normalize:
+            raise ValueError("build_transforms(resize=False) hands native-size uint8 frames to "
+                             "resize_normalize_on_device: it requires normalize=False")
+        return Compose([ToUint8HWC()])
     steps: List[Callable] = [
         Resize(img_size),
         RandomApply([ColorJitter(brightness=0.2, contrast=0.2, saturation=0.2, hue=0.05)], p=0.5),
@@ -167,4 +185,21 @@ def normalize_on_device(images_u8: torch.Tensor, mean=IMAGENET_MEAN, std=IMAGENE
     H, W = images_u8.shape[-3], images_u8.shape[-2]
     flat = images_u8.reshape(-1, H, W, 3)
     out = nat.image_normalize_u8(flat, mean, std)
+    return out.view(*lead, 3, H, W)
+
+
+def resize_normalize_on_device(images_u8: torch.Tensor, img_size, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+    """[B, V, Hs, Ws, 3] (or [N, Hs, Ws, 3]) uint8 on the GPU, at the frames' native size -> [B, V, 3, H, W] fp32
+    Resize(img_size) + ToTensor + Normalize.
+
+    One HIP launch (`bev_image_resize_normalize_u8_f32`); bit-identical to PIL's BILINEAR resize followed by ToTensor +
+    Normalize on the CPU.  A downscale of more than 17x per axis (more than 35 taps) is refused.
+    """
+    import bev_native as nat
+
+    lead = images_u8.shape[:-3]
+    Hs, Ws = images_u8.shape[-3], images_u8.shape[-2]
+    H, W = int(img_size[0]), int(img_size[1])
+    flat = images_u8.reshape(-1, Hs, Ws, 3)
+    out = nat.image_resize_normalize_u8(flat, (H, W), mean, std)
     return out.view(*lead, 3, H, W)

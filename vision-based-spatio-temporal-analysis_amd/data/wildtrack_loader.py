@@ -23,7 +23,10 @@ transform pipeline); the inverse homography of each camera is computed once per 
 once per annotated box (same matrices), and the bottom-centre points of one camera are projected
 as one batch (float32 matmul, equal to the per-point product within fp32 rounding);
 `images_uint8=True` makes __getitem__ return [V, H, W, 3] uint8 for on-device normalisation
-(`data.transforms.normalize_on_device`).
+(`data.transforms.normalize_on_device`); `native_size=True` (implies uint8) returns the decoded frames at their own
+size, [V, Hs, Ws, 3], with no Resize and no ColorJitter, for `data.transforms.resize_normalize_on_device` (the
+deterministic ingest; data/transforms.py says why the jitter cannot stay).  Frames of one dataset share a size, as
+Wildtrack's do, so `collate_fn` stacks them unchanged.
 
 Not on the hot path: this is host I/O that feeds it (JPEG/PNG decode in DataLoader workers).
 """
@@ -313,14 +316,16 @@ def _frame_centres(data: Any, H_i2w: List[torch.Tensor]) -> List[List[float]]:
 class WildtrackDataset(torch.utils.data.Dataset):
     """Multi-view Wildtrack frames (wildtrack_loader.py:250-386)."""
 
-    def __init__(self, cfg: Dict[str, Any], images_uint8: bool = False):
+    def __init__(self, cfg: Dict[str, Any], images_uint8: bool = False, native_size: bool = False):
         self.cfg = cfg
         self.data_root = Path(cfg["DATA"]["DATA_ROOT"]).resolve()
         self.views = int(cfg["DATA"]["VIEWS"])
         _, H, W = cfg["DATA"]["IMG_SIZE"]
         self.img_size = (int(H), int(W))
-        self.images_uint8 = bool(images_uint8)
-        self.transform = build_transforms(img_size=self.img_size, normalize=not self.images_uint8)
+        self.native_size = bool(native_size)
+        self.images_uint8 = bool(images_uint8) or self.native_size
+        self.transform = build_transforms(img_size=self.img_size, normalize=not self.images_uint8,
+                                          resize=not self.native_size)
         wh = cfg.get("LOSS", {}).get("DEFAULT_BOX_WH", [0.6, 0.6])
         self.default_box_wh = (float(wh[0]), float(wh[1]))
 
