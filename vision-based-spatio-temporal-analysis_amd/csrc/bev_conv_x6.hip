@@ -1114,32 +1114,45 @@ int dispatch_x6(const ConvX &a0, hipStream_t st) {
 // exact-f32 k_stem, with the products of the other trunk layers: per 16-deep k slice six v_mfma_f32_32x32x16_bf16
 // (32 cycles each) instead of eight v_mfma_f32_32x32x2_f32 (64 cycles), 2.67x fewer matrix-core cycles.
 // Workgroup = 8 waves, tile = 8 output rows x 64 columns x 64 channels, wave w owns output row w (2 x 2 MFMA tiles
-// of 32 pixels x 32 channels).  The tile's input patch (3 ch x 21 rows x 133 cols) sits in LDS as fp32 even / odd
-// column planes exactly as k_stem keeps it (stride 2: tap kx of output column ox is plane kx & 1 at ox + kx / 2),
-// so each A element is a ds_read_b32 at a compile-time offset; a lane's 8 consecutive k (the split panel's order,
-// k = (ky * 7 + kx) * 3 + ci, 147 taps padded to 160) are read, split into h / m / l and fed as three bf16
-// fragments.  The weights' split panel (fragment order, the first two 32-column blocks: 60 KiB) is copied into LDS
-// once per workgroup, so B fragments are conflict-free ds_read_b128.  Persistent over tiles; the next tile's patch
-// is fetched into registers during the MFMAs.  fp32-tolerance equal to k_stem (summation order), as every split
-// conv is to its exact-f32 counterpart.
+// of 32 pixels x 32 channels).
+// K order inside the kernel: k' = (ky, ci, kx8) -- 21 runs (ky, ci) of 8 slots, slots 0..6 = kx, slot 7 padding; a
+// 16-deep slice is two runs, half-wave h of slice sl takes run 2 sl + h: 22 runs = 11 slices, the 22nd run padding.
+// A lane's 8 fragment elements are then 8 CONTIGUOUS input columns of one patch row (stride 2: output column ox,
+// slot j = patch column 2 ox + j).  The tile's input patch (3 ch x 21 rows x 133 cols) is split into h / m / l once,
+// when it is written to LDS (each input value serves ~12 (tap, pixel) products), as three row-major bf16 planes
+// [ci][row][PITCH], so a plane's A fragment is 16 contiguous bytes at the dword 32 mt + r32 of its row: two
+// ds_read2_b32 (dword alignment is all they need) straight into the registers the MFMA reads -- per slice one select
+// of the half-wave's run offset and no per-element packing (the (ky, kx, ci) order this replaced cost one select,
+// two LDS reads and ~5 shift / and / perm per element: ~190 VALU for a slice's 24 MFMAs).
+// Padding that must not leak: slot 7 is patch column 2 ox + 7, input column 2 ox + 4 -- OUTSIDE the pixel's 7x7 field
+// (and, for ox = 63, the never-written column 133) -- so a NaN / Inf there times its zero weight would be a NaN
+// outside the receptive field: that half-dword is cleared in every plane fragment (one v_and each).  The padded 22nd
+// run reads run 0 (inside the field) against zero weights.
+// The weights come as the generic split panel (k = (ky, kx, ci), 147 -> 160); its first two 32-column blocks are
+// permuted into the k' order while they are copied into LDS, once per persistent workgroup
+// ([cb 2][slice 11][plane 3][lane 64][8], 66 KiB, slot 7 and run 21 zero), so B fragments are conflict-free
+// ds_read_b128.  Persistent over tiles; the next tile's patch is fetched into registers during the MFMAs.
+// fp32-tolerance equal to k_stem (summation order), as every split conv is to its exact-f32 counterpart.
 namespace stem6 {
 constexpr int TW = 64, TH = 8, NTHR = 512;
 constexpr int PR = 2 * TH + 5;  // 21 input rows
 constexpr int PC = 2 * TW + 5;  // 133 input columns
-constexpr int PP = 80;          // plane pitch (67 used; = 16 mod 32 -> conflict-free stores)
-constexpr int RP = 2 * PP, CP = PR * RP, PATCH = 3 * CP;
-constexpr int NE = 3 * PR * PC;
-constexpr int PER_T = (NE + NTHR - 1) / NTHR;
-constexpr int NS = 10;            // 16-deep k slices (147 -> 160)
-constexpr int WB = 2 * NS * 3 * 512;  // bf16 of the panel's first two 32-column blocks
-// The patch is split into h / m / l once, when it is written to LDS (a dword plane of (h, m) pairs and a 16-bit plane
-// of l): each input value serves ~12 (tap, pixel) products, so splitting per use (an fp32 patch with split3 on every
-// A element: the STEM6_PRESPLIT 0 arm, last in e891532) costs ~12x the conversions; it measured the same time.
-// LDS float offset of panel k (k = (ky * 7 + kx) * 3 + ci) relative to (output row 0, output column 0) of the patch;
-// the padding k >= 147 reads tap 0 (its weight is zero)
-__host__ __device__ constexpr int koff(int k) {
-    return k >= 147 ? 0 : (k % 3) * CP + (k / 21) * RP + (((k / 3) % 7) & 1) * PP + (((k / 3) % 7) >> 1);
-}
+// Row pitch in bf16: >= 134 (slot 7 of output column 63 is column 133) and even (rows start on a dword).  A
+// ds_read2_b32 is served as two ds_read_b32, each in two groups of 32 lanes with banks (a / 4) mod 32: the two
+// half-waves (different runs, so different rows) are different groups and never conflict whatever the pitch, and a
+// half-wave's 32 lanes read 32 consecutive dwords -- conflict-free.  136 = the smallest such pitch that also starts
+// every row on a 16-byte boundary.
+constexpr int PITCH = 136;
+constexpr int PLANE = 3 * PR * PITCH;  // bf16 per plane
+constexpr int PER_T = 17;              // patch elements staged per thread (stem6_fetch)
+constexpr int NRUN = 3 * 7;           // (ky, ci) runs
+constexpr int NS = (NRUN + 2) / 2;    // 11 16-deep k' slices
+constexpr int WB = 2 * NS * 3 * 512;  // bf16 of the two permuted 32-column blocks
+constexpr int S_PANEL = 10;           // the generic panel's slices (147 -> 160)
+// bf16 offset of run (ky, ci) = (run / 3, run % 3) relative to the patch row of output row 0; the padded run reads run 0
+__host__ __device__ constexpr int roff(int run) { return run >= NRUN ? 0 : ((run % 3) * PR + run / 3) * PITCH; }
+static_assert(PITCH >= 2 * TW + 6 && PITCH % 2 == 0, "slot 7 of the last output column inside the row");
+static_assert(4 * 34 * 64 * 4 <= 3 * PLANE * 2, "the pool epilogue's row exchange fits in the patch");
 }  // namespace stem6
 
 struct StemX6Args {
@@ -1155,7 +1168,12 @@ struct StemX6Args {
     int Hp, Wp;
 };
 
-__device__ __forceinline__ void stem6_fetch(const StemX6Args &a, int64_t t, int tid, float (&pv)[stem6::PER_T]) {
+// Which patch elements a thread stages (the same for every tile, so a tile costs no index arithmetic beyond its
+// origin): column c = tid & 127 of the 63 plane rows cr = ci * 21 + r = (tid >> 7) + 4 i, i = 0..15, and, as element 16,
+// one of the 63 x 5 elements of columns 128..132 (row tid >> 3, column 128 + (tid & 7)).  Elements outside the image
+// (the conv's zero padding) or outside the patch are loaded from the image's first pixel and zeroed at stem6_put by
+// the returned mask (bit i = element i is a pixel of the image).
+__device__ __forceinline__ unsigned stem6_fetch(const StemX6Args &a, int64_t t, int tid, float (&pv)[stem6::PER_T]) {
     using namespace stem6;
     const int tx = (int)(t % a.nTx);
     const int64_t r_ = t / a.nTx;
@@ -1163,32 +1181,35 @@ __device__ __forceinline__ void stem6_fetch(const StemX6Args &a, int64_t t, int 
     const int64_t img = r_ / a.nTy;
     const int row0 = 2 * ty * TH - 3, col0 = 2 * tx * TW - 3;
     const float *xi = a.x + img * 3 * (int64_t)a.H * a.W;
+    unsigned in = 0;
 #pragma unroll
     for (int i = 0; i < PER_T; ++i) {
-        const int e = tid + NTHR * i;
-        const int cr = e / PC, c = e - cr * PC;
-        const int ci = cr / PR, r = cr - ci * PR;
+        const int cr = i < PER_T - 1 ? (tid >> 7) + 4 * i : tid >> 3;
+        const int c = i < PER_T - 1 ? (tid & 127) : 2 * TW + (tid & 7);
+        const int ci = (cr >= PR) + (cr >= 2 * PR), r = cr - ci * PR;
         const int gy = row0 + r, gx = col0 + c;
-        const bool in = e < NE && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        pv[i] = *(in ? xi + ((int64_t)ci * a.H + gy) * a.W + gx : (const float *)g_xzero4);
+        const bool ok = cr < 3 * PR && c < PC && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
+        pv[i] = xi[ok ? ((int64_t)ci * a.H + gy) * a.W + gx : 0];
+        in |= (unsigned)ok << i;
     }
+    return in;
 }
 
-__device__ __forceinline__ void stem6_put(float *pl, int tid, const float (&pv)[stem6::PER_T]) {
+// split once, when the patch is written: three ds_write_b16 per element at compile-time offsets of the thread's base
+__device__ __forceinline__ void stem6_put(__bf16 *pl, int tid, const float (&pv)[stem6::PER_T], unsigned in) {
     using namespace stem6;
+    __bf16 *q = pl + (tid >> 7) * PITCH + (tid & 127);
 #pragma unroll
     for (int i = 0; i < PER_T; ++i) {
-        const int e = tid + NTHR * i;
-        if (e < NE) {
-            const int cr = e / PC, c = e - cr * PC;
-            const int ci = cr / PR, r = cr - ci * PR;
-            const int o = ci * CP + r * RP + (c & 1) * PP + (c >> 1);
-            // pl = the (h, m) dword plane, followed by the l plane (PATCH bf16)
+        const bool last = i == PER_T - 1;
+        // plane row 4 i + (tid >> 7) exists (i = 15: rows 60..62); the tail element is a column < 133 of a row < 63
+        if (last ? (tid >> 3) < 3 * PR && (tid & 7) < PC - 2 * TW : i < PER_T - 2 || (tid >> 7) < 3 * PR - 4 * i) {
+            __bf16 *o = last ? pl + (tid >> 3) * PITCH + 2 * TW + (tid & 7) : q + 4 * i * PITCH;
             __bf16 hh, mm, ll;
-            split3(pv[i], hh, mm, ll);
-            reinterpret_cast<unsigned *>(pl)[o] = (unsigned)__builtin_bit_cast(unsigned short, hh) |
-                                                  ((unsigned)__builtin_bit_cast(unsigned short, mm) << 16);
-            reinterpret_cast<__bf16 *>(pl + PATCH)[o] = ll;
+            split3((in >> i) & 1u ? pv[i] : 0.0f, hh, mm, ll);
+            o[0] = hh;
+            o[PLANE] = mm;
+            o[2 * PLANE] = ll;
         }
     }
 }
@@ -1212,25 +1233,35 @@ __device__ __forceinline__ float pool_mx(float m, float v) { return max_nan(m, v
 template <bool POOL>
 __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
     using namespace stem6;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[WB * 2 + PATCH * 6];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[WB * 2 + 3 * PLANE * 2];
     __bf16 *wl = (__bf16 *)lds_raw;
-    float *pl = (float *)(lds_raw + WB * 2);
+    __bf16 *pl = (__bf16 *)(lds_raw + WB * 2);  // the h, m, l planes
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
-    // the split panel's blocks 0 and 1 ([cb][slice][plane][64 lanes][8]) are its first WB bf16: a straight copy
-    for (int e = tid; e < WB / 8; e += NTHR) reinterpret_cast<u32x4 *>(wl)[e] = reinterpret_cast<const u32x4 *>(a.wp)[e];
+    // the split panel's blocks 0 and 1, permuted from k = (ky, kx, ci) into [cb][slice][plane][64 lanes][8] of the k'
+    // order: fragment lane (h, n) of slice sl holds run 2 sl + h of channel 32 cb + n, slot 7 and run 21 zero
+    for (int f = tid; f < WB / 8; f += NTHR) {
+        const int ln = f & 63, fr = f >> 6, p = fr % 3, sl = (fr / 3) % NS, cb = fr / (3 * NS);
+        const int run = 2 * sl + (ln >> 5), ky = run / 3, ci = run - 3 * ky, n = 32 * cb + (ln & 31);
+        const unsigned short *src = reinterpret_cast<const unsigned short *>(a.wp);
+        unsigned w[8];
+#pragma unroll
+        for (int kx = 0; kx < 7; ++kx)
+            w[kx] = run < NRUN ? (unsigned)src[frag_index(n, (ky * 7 + kx) * 3 + ci, p, S_PANEL)] : 0u;
+        reinterpret_cast<u32x4 *>(wl)[f] = (u32x4){w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6]};
+    }
     float pv[PER_T];
     int64_t t = blockIdx.x;
-    stem6_fetch(a, t < a.ntiles ? t : 0, tid, pv);
-    stem6_put(pl, tid, pv);
+    unsigned pin = stem6_fetch(a, t < a.ntiles ? t : 0, tid, pv);
+    stem6_put(pl, tid, pv, pin);
     __syncthreads();
 
-    const float *P = pl + wave * 2 * RP + r32;  // output row `wave`, column r32 (+ 32 for the second M tile)
-    const __bf16 *PL = reinterpret_cast<const __bf16 *>(pl + PATCH) + wave * 2 * RP + r32;  // its l plane
+    // output row `wave`, column r32 (+ 32 for the second M tile): slot 0 of run 0 in the h plane
+    const __bf16 *P = pl + wave * 2 * PITCH + 2 * r32;
     const float b0 = (r32 < a.Co) ? a.bias[r32] : 0.0f;
     const float b1 = (32 + r32 < a.Co) ? a.bias[32 + r32] : 0.0f;
     for (; t < a.ntiles; t += gridDim.x) {
         const int64_t tn = t + gridDim.x;
-        stem6_fetch(a, tn < a.ntiles ? tn : t, tid, pv);  // in flight during the MFMAs
+        pin = stem6_fetch(a, tn < a.ntiles ? tn : t, tid, pv);  // in flight during the MFMAs
         f32x16 acc[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -1239,9 +1270,11 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
 #pragma unroll
         for (int sl = 0; sl < NS; ++sl) {
             int hv = h;
-            asm volatile("" : "+v"(hv));  // per slice: the h selects stay cndmasks, not 160 hoisted lane offsets
-            const __bf16 *wlb = wl + lane * 8;
-            asm volatile("" : "+v"(wlb));  // per slice: the weight fragments are re-read, not held across tiles
+            asm volatile("" : "+v"(hv));  // per slice: the run select stays one cndmask, not 11 hoisted lane offsets
+            const __bf16 *Pr = P + (hv ? roff(2 * sl + 1) : roff(2 * sl));  // the half-wave's run
+            int wo = lane * 8;
+            asm volatile("" : "+v"(wo));  // per slice: the weight fragments are re-read, not held across tiles
+            const __bf16 *wlb = wl + wo;  // (the offset, not the pointer, is opaque: the reads stay ds_read_b128)
             bf16x8 fb[2][3];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -1252,13 +1285,10 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
             for (int mt = 0; mt < 2; ++mt) {
                 bf16x8 fa[3];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int o0 = koff(16 * sl + e), o1 = koff(16 * sl + 8 + e);
-                    const int o = 32 * mt + (hv ? o1 : o0);
-                    const unsigned hm = reinterpret_cast<const unsigned *>(P)[o];
-                    fa[0][e] = __builtin_bit_cast(__bf16, (unsigned short)(hm & 0xffffu));
-                    fa[1][e] = __builtin_bit_cast(__bf16, (unsigned short)(hm >> 16));
-                    fa[2][e] = PL[o];
+                for (int p = 0; p < 3; ++p) {
+                    // slots 0..7 = patch columns 2 ox .. 2 ox + 7 of the run's row; slot 7 (outside the field) cleared
+                    const unsigned *q = reinterpret_cast<const unsigned *>(Pr + p * PLANE + 64 * mt);
+                    fa[p] = __builtin_bit_cast(bf16x8, (u32x4){q[0], q[1], q[2], q[3] & 0xffffu});
                 }
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -1312,7 +1342,7 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                         hp[mt][b][0][j] = pool_mx(hp[mt][b][0][j], h ? pa3[mt][j][b] : prev0);
                     }
             __syncthreads();  // every wave is done reading the patch: its LDS holds the row exchange
-            float *xl = pl;   // [odd wave][34][64 lanes]
+            float *xl = reinterpret_cast<float *>(pl);  // [odd wave][34][64 lanes]
             if (wave & 1) {
                 float *o = xl + (wave >> 1) * 34 * 64 + lane;
 #pragma unroll
@@ -1327,6 +1357,24 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                 o[33 * 64] = c63[1];
             }
             __syncthreads();
+            // the row above (p = 0 has none: it re-reads the row below, unused) and below: all 68 reads issued before
+            // the first maximum, not one LDS round trip per value
+            const int p = wave >> 1;
+            float uv[34], dv[34];
+            if (!(wave & 1)) {
+                const float *up = xl + (p > 0 ? p - 1 : p) * 34 * 64 + lane, *dn = xl + p * 34 * 64 + lane;
+#pragma unroll
+                for (int e = 0; e < 34; ++e) {
+                    dv[e] = dn[e * 64];
+                    uv[e] = up[e * 64];
+                }
+            }
+            // The next patch goes into LDS BEFORE this tile's stores are issued: stem6_put waits for its loads with
+            // counted vmcnt, which -- loads and stores sharing that counter, in order -- would wait for every store
+            // issued after them too (a store's round trip per tile, on all eight waves).  Issued last, the stores
+            // drain during the next tile's MFMAs.
+            __syncthreads();  // the row exchange is read
+            stem6_put(pl, tid, pv, pin);
             const int64_t tile = t;
             if (wave == TH - 1) {  // the last row: next tile row's pooled row 0, and column 63 alone (pooled row 4)
                 float *eb = a.edge_b + tile * (32 * 64);
@@ -1344,8 +1392,6 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                     a.edge_r[(tile * 5 + 4) * 64 + 32 + r32] = c63[1];
                 }
             } else if (!(wave & 1)) {
-                const int p = wave >> 1;
-                const float *up = xl + (p - 1) * 34 * 64 + lane, *dn = xl + p * 34 * 64 + lane;
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -1354,15 +1400,14 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                         for (int pc = 0; pc < 2; ++pc)
 #pragma unroll
                             for (int j = 0; j < 2; ++j) {
-                                const int e = (((mt * 4 + b) * 2 + pc) * 2 + j) * 64;
-                                float m = pool_mx(hp[mt][b][pc][j], dn[e]);
-                                if (p > 0) m = pool_mx(m, up[e]);
-                                hp[mt][b][pc][j] = m;
+                                const int e = ((mt * 4 + b) * 2 + pc) * 2 + j;
+                                const float m = pool_mx(hp[mt][b][pc][j], dv[e]);
+                                hp[mt][b][pc][j] = p > 0 ? pool_mx(m, uv[e]) : m;
                             }
-                float e0 = pool_mx(c63[0], dn[32 * 64]), e1 = pool_mx(c63[1], dn[33 * 64]);
+                float e0 = pool_mx(c63[0], dv[32]), e1 = pool_mx(c63[1], dv[33]);
                 if (p > 0) {
-                    e0 = pool_mx(e0, up[32 * 64]);
-                    e1 = pool_mx(e1, up[33 * 64]);
+                    e0 = pool_mx(e0, uv[32]);
+                    e1 = pool_mx(e1, uv[33]);
                 }
                 if (h) {
                     a.edge_r[(tile * 5 + p) * 64 + r32] = e0;
@@ -1392,6 +1437,8 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
             const int64_t img = r_ / a.nTy;
             const int oy = ty * TH + wave;
             const int oxb = tx * TW;
+            __syncthreads();  // every wave is done reading the patch
+            stem6_put(pl, tid, pv, pin);  // before the stores, as in the pooled form
             if (oy < a.Ho) {
                 float *yr = a.y + ((img * a.Ho + oy) * (int64_t)a.Wo) * a.Co;
 #pragma unroll
@@ -1412,9 +1459,7 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                     }
             }
         }
-        __syncthreads();  // every wave is done reading the patch
-        stem6_put(pl, tid, pv);
-        __syncthreads();
+        __syncthreads();  // the next patch is in LDS
     }
 }
 
