@@ -36,7 +36,9 @@ extern "C" {
 /* 16: the pre-split chain that also ran the next block's 1x1 conv in its epilogue left (last tree: 5535b89).
  * 17: the depthwise kernels that only a non-default knob could launch left, with the knob values that selected them
  *     (DW_RUN 1 / 2); CONV_X6_KERNEL 2, an alias of 0, is rejected (last tree: e891532).
- * ABI version (bumped on any signature change, and when public constants or accepted values go): 17. */
+ * 18: the BatchNorm tile partials that bev_conv2d_h16_bnstats_f32 / _ex_f32 write and
+ *     bev_batchnorm_finalize_tiles_f32 reads are double, not float (last tree: daba03b).
+ * ABI version (bumped on any signature change, and when public constants or accepted values go): 18. */
 int bev_abi_version(void);
 
 /* host: provenance -- the first 16 hex digits of sha256 over the library's HIP sources and headers (the
@@ -540,18 +542,19 @@ int64_t bev_conv_h16_stat_tiles(int64_t M);
 /* device: bev_conv2d_h16_f32 (act 0, no residual, ldy == Co; Ci % 64 == 0) that also writes the BatchNorm batch
  * statistics of its output, so the train-mode BN after the conv does not read it back: tile_stats
  * [Co][bev_conv_h16_stat_tiles(M)][2] = per channel and 128-row tile (sum, sum of squared deviations from the tile
- * mean), fp32; combine with bev_batchnorm_finalize_tiles_f32.  Replaces the conv -> BatchNorm2d(train) pair of the
+ * mean), double (ABI 18; fp32 before: a tile mean known to 2^-24 cost 1e-4 of the variance at mean / std = 6000);
+ * combine with bev_batchnorm_finalize_tiles_f32.  Replaces the conv -> BatchNorm2d(train) pair of the
  * timm trunk under autocast (cnn_encoder.py:26, train.py:238-247). */
 int bev_conv2d_h16_bnstats_f32(const float *x, int N, int H, int W, int Ci, const uint16_t *packed, const float *bias,
                                int Co, int KH, int KW, int stride, int pad, int dilation, float *y, int Ho, int Wo,
-                               float *tile_stats, void *stream);
+                               double *tile_stats, void *stream);
 
 /* bev_conv2d_h16_f32 / _bnstats_f32 in one entry, with the operand x optionally STORED in fp16 (x_half = 1: uint16
  * storage of _Float16, 8-B aligned, Ci % 64 == 0) -- the values the fp32-operand kernel rounds x to while staging,
  * so the result is bit-identical; tile_stats may be NULL (else act 0, no residual, ldy == Co). */
 int bev_conv2d_h16_ex_f32(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
                           const float *bias, const float *residual, int Co, int KH, int KW, int stride, int pad,
-                          int dilation, int act, float *y, int ldy, int Ho, int Wo, float *tile_stats, void *stream);
+                          int dilation, int act, float *y, int ldy, int Ho, int Wo, double *tile_stats, void *stream);
 
 /* The "f16" inference arithmetic (the reference validates in eval() under autocast(float16), train.py:285-286):
  * bev_conv2d_h16_ex_f32's convolution with fp16 activations from layer to layer,
@@ -746,9 +749,9 @@ int bev_batchnorm_train_fwd_f32(const float *z, int64_t M, int C, float eps, flo
                                 float *scale, float *shift, void *workspace, void *stream);
 
 /* device: bev_batchnorm_train_fwd_f32's outputs (mean, rstd, scale, shift, running-stat update) from per-tile
- * partials (sum, M2 about the tile mean) [C][ntiles][2] of z [M][C] in tiles of rows_per_tile rows (the last
+ * partials (sum, M2 about the tile mean) [C][ntiles][2] (double) of z [M][C] in tiles of rows_per_tile rows (the last
  * one ragged), combined in double: mean = sum of sums / M, M2 = sum of (M2_k + n_k (mean_k - mean)^2). */
-int bev_batchnorm_finalize_tiles_f32(const float *tile_stats, int ntiles, int rows_per_tile, int64_t M, int C,
+int bev_batchnorm_finalize_tiles_f32(const double *tile_stats, int ntiles, int rows_per_tile, int64_t M, int C,
                                      float eps, float momentum, const float *gamma, const float *beta,
                                      float *running_mean, float *running_var, float *mean, float *rstd, float *scale,
                                      float *shift, void *stream);

@@ -46,7 +46,7 @@ def test_ctypes_signatures_cover_header(lib):
 
 def test_abi_version(lib):
     import bev_native
-    assert lib.bev_abi_version() == bev_native.ABI_VERSION == 17
+    assert lib.bev_abi_version() == bev_native.ABI_VERSION == 18
 
 
 def test_abi_16_retired_the_fused_next_chain(lib):

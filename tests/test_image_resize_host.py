@@ -108,7 +108,7 @@ def test_header_library_and_signatures(lib):
     for e in ENTRIES:
         assert re.search(r"\b%s\s*\(" % e, txt), e
         assert e in exported and e in bev_native.SIGNATURES and hasattr(lib, e)
-    assert lib.bev_abi_version() == bev_native.ABI_VERSION == 17
+    assert lib.bev_abi_version() == bev_native.ABI_VERSION == 18
 
 
 # Argument order of the launch and one accepted argument set; the addresses are made up and never handed to a kernel:

@@ -20,7 +20,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libbev_mi355x.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 BEV_ERR_ARGS = -1  # include/bev_mi355x.h: an argument the kernel cannot take
 
 FUSE_MODES = {"sum": 0, "mean": 1, "max": 2}
@@ -942,8 +942,8 @@ H16_STAT_ROWS = 128  # rows per BatchNorm statistics tile of conv2d_nhwc_h16_bns
 
 def conv2d_nhwc_h16_bnstats(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: int, KW: int, stride: int, pad: int):
     """The fp16-operand conv of a train-mode BatchNorm layer (no bias, no activation; Ci % 64 == 0) with the BN batch
-    statistics taken in its epilogue: -> (z [N,Ho,Wo,Co] fp32, tile partials [tiles, Co, 2] = per 128-row tile
-    (sum, sum of squared deviations from the tile mean), channel-major [Co, tiles, 2]) for batchnorm_finalize_tiles."""
+    statistics taken in its epilogue: -> (z [N,Ho,Wo,Co] fp32, tile partials = per 128-row tile
+    (sum, sum of squared deviations from the tile mean) in float64, channel-major [Co, tiles, 2]) for batchnorm_finalize_tiles."""
     x = x.contiguous()
     _require_gpu(x)
     _require_panel(packed, torch.float16, "conv2d_nhwc_h16_bnstats")
@@ -952,7 +952,7 @@ def conv2d_nhwc_h16_bnstats(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: 
     z = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.float32)
     nt = lib().bev_conv_h16_stat_tiles(N * Ho * Wo)
     _check(0 if nt > 0 else nt, "bev_conv_h16_stat_tiles")
-    tiles = torch.empty(Co, nt, 2, device=x.device, dtype=torch.float32)
+    tiles = torch.empty(Co, nt, 2, device=x.device, dtype=torch.float64)
     with _span("conv", x):
         rc = lib().bev_conv2d_h16_bnstats_f32(_ptr(x), N, H, W, Ci, _ptr(packed), None, Co, KH, KW, stride, pad, 1,
                                               _ptr(z), Ho, Wo, _ptr(tiles), _stream(x))
@@ -989,7 +989,7 @@ def conv2d_h16_any(x: torch.Tensor, packed: torch.Tensor, Co: int, KH: int, KW: 
     if stats:
         nt = lib().bev_conv_h16_stat_tiles(N * Ho * Wo)
         _check(0 if nt > 0 else nt, "bev_conv_h16_stat_tiles")
-        tiles = torch.empty(Co, nt, 2, device=x.device, dtype=torch.float32)
+        tiles = torch.empty(Co, nt, 2, device=x.device, dtype=torch.float64)
     if residual is not None:
         residual = residual.contiguous()
     with _span("conv", x):
@@ -1206,7 +1206,9 @@ def batchnorm_finalize_tiles(tiles: torch.Tensor, M: int, gamma, beta, running_m
                              momentum: float):
     """batchnorm_train_fwd's outputs (mean, rstd, scale, shift; running stats updated in place if given) from the
     per-tile partials of conv2d_nhwc_h16_bnstats over M rows."""
-    _require_gpu(tiles, gamma, beta, running_mean, running_var)
+    _require_gpu(gamma, beta, running_mean, running_var)
+    if not tiles.is_cuda or tiles.dtype != torch.float64 or not tiles.is_contiguous():
+        raise HipError("batchnorm_finalize_tiles: the float64 tile partials of conv2d_nhwc_h16_bnstats")
     C, nt, _ = tiles.shape
     dev = tiles.device
     mean, rstd, scale, shift = (torch.empty(C, device=dev) for _ in range(4))

@@ -1,7 +1,7 @@
 // bev_bn.hip -- BatchNorm with batch statistics for training the backbone trunk (timm's BN in
 // model.train(), reference train.py:222), on NHWC activations viewed as rows [M][C] (M = N*H*W), fp32:
 //
-//   forward   k_bn_partial<Stats>  per block of rows: per-channel (sum z, sum z^2) in double
+//   forward   k_bn_partial<Stats>  per block of rows: per-channel (sum z, sum z^2), squared and summed in double
 //             k_bn_finalize        mean, biased var, rstd = 1/sqrt(var + eps), scale = gamma*rstd,
 //                                  shift = beta - mean*scale; running_mean / running_var updated with
 //                                  the momentum rule and the unbiased variance (torch's train-mode BN)
@@ -35,12 +35,19 @@ constexpr int BN_ROWS = 1024;  // rows per block
 constexpr int BN_QB = 64;      // channel quads per block (256 channels)
 constexpr int BN_U = 4;        // rows per load batch of the streaming passes
 
+// A functor of k_bn_partial_body: at() loads element i's operands (a, b) -- the batched loop keeps a batch of them in
+// flight -- and add2() adds the element's term of the second sum; the first sum is of a.
+// Stats: the second sum is of z^2, squared in double (exact: 48 significant bits) -- an fp32 square carries a rounding
+// error of 2^-24 mean^2, which is the whole variance of a channel whose mean is a few thousand spreads from zero
+// (var = E[z^2] - mean^2 cancels); k_gn_partial squares the same way.  b is not used.
+__device__ __forceinline__ void add_b(double (&t)[4], const float4 &, const float4 &b) {
+    t[0] += b.x; t[1] += b.y; t[2] += b.z; t[3] += b.w;
+}
 struct Stats {  // (z, z^2)
     const float *z;
-    __device__ void at(int64_t i, int, float4 &a, float4 &b) const {
-        const float4 v = *(const float4 *)(z + i);
-        a = v;
-        b = make_float4(v.x * v.x, v.y * v.y, v.z * v.z, v.w * v.w);
+    __device__ void at(int64_t i, int, float4 &a, float4 &) const { a = *(const float4 *)(z + i); }
+    static __device__ __forceinline__ void add2(double (&t)[4], const float4 &a, const float4 &) {
+        t[0] += (double)a.x * a.x; t[1] += (double)a.y * a.y; t[2] += (double)a.z * a.z; t[3] += (double)a.w * a.w;
     }
 };
 
@@ -110,6 +117,7 @@ __device__ __forceinline__ void act_grad_t(float (&g)[4], const float4 d, const 
 
 template <int ACT>
 struct GradsT {  // Grads with a compile-time activation
+    static __device__ __forceinline__ void add2(double (&t)[4], const float4 &a, const float4 &b) { add_b(t, a, b); }
     const float *dy, *y, *z, *mean, *rstd, *scale, *shift;
     __device__ void at(int64_t i, int c, float4 &a, float4 &b) const {
         const float4 d = *(const float4 *)(dy + i), v = *(const float4 *)(z + i);
@@ -156,14 +164,14 @@ __device__ __forceinline__ void k_bn_partial_body(const F &f, int64_t M, int C, 
 #pragma unroll
             for (int u = 0; u < BN_U; ++u) {
                 s[0] += a[u].x; s[1] += a[u].y; s[2] += a[u].z; s[3] += a[u].w;
-                t[0] += b[u].x; t[1] += b[u].y; t[2] += b[u].z; t[3] += b[u].w;
+                F::add2(t, a[u], b[u]);
             }
         }
         for (; r < r1; r += nph) {
             float4 a, b;
             f.at(r * C + 4 * qg, 4 * qg, a, b);
             s[0] += a.x; s[1] += a.y; s[2] += a.z; s[3] += a.w;
-            t[0] += b.x; t[1] += b.y; t[2] += b.z; t[3] += b.w;
+            F::add2(t, a, b);
         }
     }
 #pragma unroll
@@ -243,7 +251,7 @@ __global__ __launch_bounds__(FIN_C * FIN_P) void k_bn_finalize(const double *__r
 }
 
 // BatchNorm statistics from the conv epilogue's per-tile partials (k_conv_h16b with stats): channel c's tiles
-// part[c][k] = (sum, M2 about the tile mean) over n_k = min(rows, M - k rows) rows, fp32.  One workgroup per
+// part[c][k] = (sum, M2 about the tile mean) over n_k = min(rows, M - k rows) rows, double.  One workgroup per
 // channel, two passes over its (contiguous) tiles in double: mean = sum_k sum_k / M, then
 // M2 = sum_k (M2_k + n_k (mean_k - mean)^2) -- the exact combination (Chan et al.), no per-tile division chain.
 // Same outputs and running-stat rule as k_bn_finalize.
@@ -258,7 +266,7 @@ __device__ __forceinline__ double ft_block_sum(double v, double *red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ __launch_bounds__(FT_T) void k_bn_finalize_tiles(const float *__restrict__ part, int ntiles, int rows,
+__global__ __launch_bounds__(FT_T) void k_bn_finalize_tiles(const double *__restrict__ part, int ntiles, int rows,
                                                               int64_t M, int C, float eps, float momentum,
                                                               const float *__restrict__ gamma,
                                                               const float *__restrict__ beta,
@@ -268,17 +276,17 @@ __global__ __launch_bounds__(FT_T) void k_bn_finalize_tiles(const float *__restr
                                                               float *__restrict__ scale, float *__restrict__ shift) {
     __shared__ double red[4];
     const int c = blockIdx.x;
-    const float2 *pc = reinterpret_cast<const float2 *>(part) + (size_t)c * ntiles;
+    const double2 *pc = reinterpret_cast<const double2 *>(part) + (size_t)c * ntiles;
     double s = 0.0;
-    for (int k = threadIdx.x; k < ntiles; k += FT_T) s += (double)pc[k].x;
+    for (int k = threadIdx.x; k < ntiles; k += FT_T) s += pc[k].x;
     const double mu = ft_block_sum(s, red) / (double)M;
     double q = 0.0;
     for (int k = threadIdx.x; k < ntiles; k += FT_T) {
         const int64_t left = M - (int64_t)k * rows;
         const double nk = (double)(left < rows ? left : rows);
-        const float2 t = pc[k];
-        const double d = (double)t.x / nk - mu;
-        q += (double)t.y + nk * d * d;
+        const double2 t = pc[k];
+        const double d = t.x / nk - mu;
+        q += t.y + nk * d * d;
     }
     const double m2 = ft_block_sum(q, red);
     if (threadIdx.x != 0) return;
@@ -506,6 +514,7 @@ static void launch_bn_bwd_apply_q(dim3 g, hipStream_t st, const float *dy, const
 
 // ---- per-image channel sums and channel affine (SqueezeExcite training) -------------------------------
 struct Prod {  // (x * x2, unused)
+    static __device__ __forceinline__ void add2(double (&t)[4], const float4 &a, const float4 &b) { add_b(t, a, b); }
     const float *x, *x2;
     __device__ void at(int64_t i, int, float4 &a, float4 &b) const {
         const float4 v = *(const float4 *)(x + i);
@@ -585,7 +594,7 @@ int bev_batchnorm_train_fwd_f32(const float *z, int64_t M, int C, float eps, flo
     return (int)hipGetLastError();
 }
 
-int bev_batchnorm_finalize_tiles_f32(const float *tile_stats, int ntiles, int rows_per_tile, int64_t M, int C,
+int bev_batchnorm_finalize_tiles_f32(const double *tile_stats, int ntiles, int rows_per_tile, int64_t M, int C,
                                      float eps, float momentum, const float *gamma, const float *beta,
                                      float *running_mean, float *running_var, float *mean, float *rstd, float *scale,
                                      float *shift, void *stream) {

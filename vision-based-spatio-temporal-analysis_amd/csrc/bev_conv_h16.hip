@@ -65,7 +65,7 @@ struct ConvH {
     const float *__restrict__ bias;
     const float *__restrict__ res;
     float *__restrict__ y;
-    float *__restrict__ stats;  // k_conv_h16b: per (row tile, channel) BatchNorm partials (sum, M2) of the output, or null
+    double *__restrict__ stats;  // k_conv_h16b: per (row tile, channel) BatchNorm partials (sum, M2) of the output, or null
     int N, H, W, Ci, Co, KH, KW, stride, pad, dil, Ho, Wo, act, ldy, Kp;
     int64_t M;
     const float *__restrict__ in_scale;  // k_conv_h16b<.., AFF = true>: the operand affine [N][Ci] (bev_conv2d_h16_affine)
@@ -222,15 +222,19 @@ constexpr int HBK2 = 64, HROW2 = 72;  // HROW2: halves per LDS row, 64 + 8 pad =
 
 // BatchNorm statistics of the conv output z = acc + bias (training forward, BN with batch statistics), fused into
 // the epilogue so z is not read back: per output column of the 128 x 128 tile, over the tile's valid rows,
-// (sum, M2 = sum (z - sum / n)^2) in fp32 -> stats[col][row tile][2] (channel-major: the finalize reads each
-// channel's tiles contiguously); bev_batchnorm_finalize_tiles_f32 combines the tiles in double.  Two-pass around the tile mean, so the variance
-// has no E[z^2] - E[z]^2 cancellation.  Column col = n0 + wn 64 + j 32 + r32 is held by 32 rows of each lane,
-// the lane pair (h = 0, 1) and the two wm waves: lane sums, one xor-32 exchange, one LDS exchange.
+// (sum, M2 = sum (z - sum / n)^2) -> stats[col][row tile][2] in double (channel-major: the finalize reads each
+// channel's tiles contiguously); bev_batchnorm_finalize_tiles_f32 combines the tiles in double.  Two passes in fp32
+// about a pivot p = the fp32 tile mean: r = sum (z - p) and q = sum (z - p)^2 (z - p is exact, both sums are of small
+// terms), then sum = n p + r and M2 = q - r^2 / n in double -- exact identities, so neither the fp32 sum's rounding nor
+// the pivot's reaches the result.  (Stored as fp32 (sum, q) the tile mean was known to 2^-24 of the mean only, and
+// the cross term 2 (p - mean) r that the finalize could not form was 1e-4 of the variance at mean / std = 6000.)
+// Column col = n0 + wn 64 + j 32 + r32 is held by 32 rows of each lane, the lane pair (h = 0, 1) and the two wm
+// waves: lane sums, one xor-32 exchange, one LDS exchange (the second pass exchanges q and r together).
 template <int BN, int TI>
 __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&acc)[TI][2], _Float16 *ldsh, int64_t m0,
                                                int n0, int wm, int wn, int r32, int h) {
     constexpr int NRW = BN == 128 ? 2 : 4, WROWS = BN == 128 ? 64 : 32;  // row-waves sharing a column, rows each
-    float *red = reinterpret_cast<float *>(ldsh);  // [NRW][BN cols]
+    float *red = reinterpret_cast<float *>(ldsh);  // [NRW][BN cols]; the second pass: [2][NRW][BN] (q, then r), 2 KB
     const int64_t nv64 = a.M - m0;
     const int nv = nv64 < HBM ? (int)nv64 : HBM;
     float mean[2], sum[2];
@@ -265,17 +269,24 @@ __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&ac
     for (int j = 0; j < 2; ++j) {
         const int c = wn * 64 + j * 32 + r32;
         const float bv = (a.bias && n0 + c < a.Co) ? a.bias[n0 + c] : 0.0f;
-        float q = 0.0f;
+        float q = 0.0f, e = 0.0f;
 #pragma unroll
         for (int i = 0; i < TI; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = wm * WROWS + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 const float d = acc[i][j][r] + bv - mean[j];
-                if (row < nv) q = fmaf(d, d, q);
+                if (row < nv) {
+                    q = fmaf(d, d, q);
+                    e += d;
+                }
             }
         q += __shfl_xor(q, 32);
-        if (h == 0) red[wm * BN + c] = q;
+        e += __shfl_xor(e, 32);
+        if (h == 0) {
+            red[wm * BN + c] = q;
+            red[(NRW + wm) * BN + c] = e;
+        }
     }
     __syncthreads();
     if (wm == 0 && h == 0) {
@@ -283,12 +294,15 @@ __device__ __forceinline__ void h16_tile_stats(const ConvH &a, const f32x16 (&ac
         for (int j = 0; j < 2; ++j) {
             const int c = wn * 64 + j * 32 + r32;
             if (n0 + c < a.Co) {
-                float t = 0.0f;
+                float t = 0.0f, u = 0.0f;
 #pragma unroll
-                for (int w = 0; w < NRW; ++w) t += red[w * BN + c];
-                float *o = a.stats + ((int64_t)(n0 + c) * ((a.M + HBM - 1) / HBM) + m0 / HBM) * 2;
-                o[0] = sum[j];
-                o[1] = t;
+                for (int w = 0; w < NRW; ++w) {
+                    t += red[w * BN + c];
+                    u += red[(NRW + w) * BN + c];
+                }
+                double *o = a.stats + ((int64_t)(n0 + c) * ((a.M + HBM - 1) / HBM) + m0 / HBM) * 2;
+                o[0] = (double)nv * (double)mean[j] + (double)u;
+                o[1] = (double)t - (double)u * (double)u / (double)nv;
             }
         }
     }
@@ -1022,7 +1036,7 @@ struct ConvIo {
     void *y;  // output: fp32 rows of ldy >= Co words, or with y_half dense fp16 [M][Co] (Co % 8 == 0, 16-B aligned)
     int y_half, ldy;
     const void *res;                    // residual [M][Co] of y's type (fp16: not overlapping y), or null
-    float *stats;                       // BatchNorm tile partials of the raw fp32 output, or null
+    double *stats;                      // BatchNorm tile partials of the raw fp32 output, or null
     const float *in_scale, *in_shift;   // operand affine [N][Ci] (fp16 operand), both or neither
     int in_relu;
     bool deep32;  // the entry may run the 32-deep k_conv_h16: Ci % 32 == 0 is enough, CONV_H16_KERNEL 1 selects it
@@ -1175,7 +1189,7 @@ int bev_conv_pack_weights_h16(const float *w, int Co, int Ci, int KH, int KW, ui
 
 int bev_conv2d_h16_ex_f32(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,
                           const float *bias, const float *residual, int Co, int KH, int KW, int stride, int pad,
-                          int dilation, int act, float *y, int ldy, int Ho, int Wo, float *tile_stats, void *stream) {
+                          int dilation, int act, float *y, int ldy, int Ho, int Wo, double *tile_stats, void *stream) {
     const ConvIo io = {x, x_half, y, 0, ldy, residual, tile_stats, nullptr, nullptr, 0, true};
     return conv_h16(io, N, H, W, Ci, packed, bias, Co, KH, KW, stride, pad, dilation, act, Ho, Wo, stream);
 }
@@ -1191,7 +1205,7 @@ int64_t bev_conv_h16_stat_tiles(int64_t M) { return M > 0 ? (M + HBM - 1) / HBM 
 
 int bev_conv2d_h16_bnstats_f32(const float *x, int N, int H, int W, int Ci, const uint16_t *packed, const float *bias,
                                int Co, int KH, int KW, int stride, int pad, int dilation, float *y, int Ho, int Wo,
-                               float *tile_stats, void *stream) {
+                               double *tile_stats, void *stream) {
     if (!tile_stats) return BEV_ERR_ARGS;
     return bev_conv2d_h16_ex_f32(x, 0, N, H, W, Ci, packed, bias, nullptr, Co, KH, KW, stride, pad, dilation, 0, y, Co,
                                  Ho, Wo, tile_stats, stream);

@@ -627,7 +627,7 @@ constexpr int FL_T = 256, FL_MAXB = 1024;
 __device__ __forceinline__ float fl_p(float x, float &s) {
     s = 1.0f / (1.0f + expf(-x));
     const float lo = (float)1e-4, hi = (float)(1.0 - 1e-4);
-    return fminf(fmaxf(s, lo), hi);
+    return s < lo ? lo : (s > hi ? hi : s);  // torch's clamp: a NaN stays a NaN (fminf / fmaxf would return the bound)
 }
 
 __device__ __forceinline__ double fl_block_sum(double v, double *red) {
