@@ -182,6 +182,115 @@ def test_conv_h16_argument_rules_without_gpu(lib):
         assert not bad, bad
 
 
+# Argument order of the six split-bf16 (x6) conv entry points (include/bev_mi355x.h).  The four tensor entries get one
+# accepted argument set each, with N = 0 so that the answer comes before any HIP call; the two stem entries reject
+# N = 0, so their base set (N = 1) would launch and only rows with one rule broken are called.
+_X6_ORDER = {
+    "bev_conv2d_x6_f32": "x xs N H W Ci packed bias residual Co KH KW stride pad dilation act y ys ldy Ho Wo stream",
+    "bev_conv2d_dual_x6_f32": "x N Ho Wo Ci x2 H2 W2 Ci2 stride2 packed bias Co act y stream",
+    "bev_conv2d_chain_x6_f32": "x xs N H W Ci packed bias Co KH KW stride pad act packed2 bias2 Co2 residual act2 y Ho Wo "
+                               "stream",
+    "bev_conv2d_chain_dual_x6_f32": "x xs N H W Ci packed bias Co KH KW stride pad act x2 H2 W2 Ci2 stride2 packed2 bias2 "
+                                    "Co2 act2 y Ho Wo stream",
+    "bev_conv2d_stem_x6_f32": "x N H W packed bias Co relu y Ho Wo stream",
+    "bev_conv2d_stem_pool_x6_f32": "x N H W packed bias Co y Hp Wp workspace workspace_bytes stream",
+}
+_X6_PLAIN, _X6_DUAL, _X6_CHAIN, _X6_CDUAL, _X6_STEM, _X6_SPOOL = _X6_ORDER
+_X6_TENSOR = (_X6_PLAIN, _X6_DUAL, _X6_CHAIN, _X6_CDUAL)
+_X6_BASE = dict(x=0x10000, xs=None, N=0, H=8, W=8, Ci=64, packed=0x20000, bias=None, residual=None, Co=64, KH=3, KW=3,
+                stride=1, pad=1, dilation=1, act=0, y=0x30000, ys=None, ldy=64, Ho=8, Wo=8, stream=None,
+                x2=0x40000, H2=8, W2=8, Ci2=64, stride2=1, packed2=0x50000, bias2=None, Co2=256, act2=1)
+_X6_STEM_BASE = {  # 16 x 16 image -> 8 x 8 stem output; 32 x 32 -> 16 x 16 -> 8 x 8 pooled
+    _X6_STEM: dict(x=0x10000, N=1, H=16, W=16, packed=0x20000, bias=0x70000, Co=64, relu=1, y=0x30000, Ho=8, Wo=8,
+                   stream=None),
+    _X6_SPOOL: dict(x=0x10000, N=1, H=32, W=32, packed=0x20000, bias=0x70000, Co=64, y=0x30000, Hp=8, Wp=8,
+                    workspace=0xA0000, workspace_bytes=1 << 30, stream=None),
+}
+_X6_COMMON = [  # one rule violated -> -1 from every tensor entry that has the argument
+    dict(x=None), dict(xs=0x60000),                  # exactly one of x / xs
+    dict(packed=None), dict(packed2=None), dict(x2=None), dict(y=None), dict(N=-1), dict(H=0), dict(W=0), dict(Co=0),
+    dict(KH=0), dict(KW=0), dict(stride=0), dict(pad=-1), dict(act=-1), dict(act=3), dict(act2=-1), dict(act2=3),
+    dict(H2=0), dict(W2=0), dict(stride2=0), dict(Co2=0), dict(Co2=-64), dict(Co2=96),
+    dict(Ho=7), dict(Wo=9), dict(stride=2), dict(stride2=2),  # Ho / Wo inconsistent with the geometry
+    dict(H=1, pad=0, Ho=-1, Wo=6),                   # consistent, but no output row
+    dict(x=0x10008), dict(x=None, xs=0x60008), dict(packed=0x20008), dict(packed2=0x50008),  # 8 mod 16
+    dict(Ci=40),                                     # no whole K step in any entry
+]
+_X6_ROWS = (
+    [(e, {}, 0) for e in _X6_TENSOR]
+    + [(e, v, -1) for e in _X6_TENSOR for v in _X6_COMMON if set(v) <= set(_X6_ORDER[e].split())]
+    # never checked by any entry: the alignment of y, bias, bias2 and the residual
+    + [(e, v, 0) for e in _X6_TENSOR for v in (dict(y=0x30004), dict(bias=0x70004), dict(bias2=0x70004),
+                                               dict(residual=0x80004), dict(residual=0x30000))
+       if set(v) <= set(_X6_ORDER[e].split())]
+    # a pre-split operand in place of x (K steps of 32 channels)
+    + [(e, dict(x=None, xs=0x60000), 0) for e in (_X6_PLAIN, _X6_CHAIN, _X6_CDUAL)]
+    + [(e, dict(x=None, xs=0x60000, Ci=96), 0) for e in (_X6_PLAIN, _X6_CHAIN, _X6_CDUAL)]
+    + [(_X6_PLAIN, dict(Ci=48), 0), (_X6_PLAIN, dict(x=None, xs=0x60000, Ci=48), -1),  # fp32 x: 16-channel K steps
+       (_X6_PLAIN, dict(Ci=0), -1),
+       # only the plain entry has (and checks) a dilation and an output row pitch; ldy >= Co, dense rows for a
+       # residual and for split output
+       (_X6_PLAIN, dict(dilation=0), -1), (_X6_PLAIN, dict(dilation=2), -1),
+       (_X6_PLAIN, dict(dilation=2, Ho=6, Wo=6), 0),
+       (_X6_PLAIN, dict(ldy=63), -1), (_X6_PLAIN, dict(ldy=128), 0),
+       (_X6_PLAIN, dict(residual=0x80000), 0), (_X6_PLAIN, dict(residual=0x80000, ldy=128), -1),
+       # exactly one of y / ys; split output: ldy == Co, Co % 4 == 0, 8-byte aligned
+       (_X6_PLAIN, dict(ys=0x90000), -1), (_X6_PLAIN, dict(y=None, ys=0x90000), 0),
+       (_X6_PLAIN, dict(y=None, ys=0x90008), 0), (_X6_PLAIN, dict(y=None, ys=0x90004), -1),
+       (_X6_PLAIN, dict(y=None, ys=0x90000, ldy=128), -1), (_X6_PLAIN, dict(y=None, ys=0x90000, Co=62, ldy=62), -1),
+       (_X6_PLAIN, dict(Co=62, ldy=62), 0), (_X6_PLAIN, dict(y=None, ys=0x90000, residual=0x80000), 0),
+       # dual: both K parts in 16-channel steps, the shortcut operand aligned, geometry from (H2, W2, stride2)
+       (_X6_DUAL, dict(Ci=48), 0), (_X6_DUAL, dict(Ci2=48), 0), (_X6_DUAL, dict(Ci2=40), -1),
+       (_X6_DUAL, dict(Ci=0), -1), (_X6_DUAL, dict(Ci2=0), -1), (_X6_DUAL, dict(Ho=0), -1), (_X6_DUAL, dict(Wo=0), -1),
+       (_X6_DUAL, dict(x2=0x40008), -1), (_X6_DUAL, dict(stride2=2, Ho=4, Wo=4), 0), (_X6_DUAL, dict(Co=60), 0),
+       # chain: 32-channel K steps; h2 of 64 or 128 channels; Co2 in 64s
+       (_X6_CHAIN, dict(Ci=48), -1), (_X6_CHAIN, dict(Ci=96), 0), (_X6_CHAIN, dict(Co=32), -1),
+       (_X6_CHAIN, dict(Co=256), -1), (_X6_CHAIN, dict(Co=128), 0), (_X6_CHAIN, dict(Co2=64), 0),
+       (_X6_CHAIN, dict(residual=0x80000), 0), (_X6_CHAIN, dict(bias=0x70000, bias2=0x70100), 0),
+       # QUIRK: Co = 128 needs Co2 % 128 == 0 (two waves share a 32-row band), but that is checked after the N == 0
+       # return, so the empty call answers 0
+       (_X6_CHAIN, dict(Co=128, Co2=64), 0),
+       # QUIRK: the chain entries check Ci % 32 only, not its sign: with N = 0 a zero Ci is accepted
+       (_X6_CHAIN, dict(Ci=0), 0), (_X6_CDUAL, dict(Ci=0), 0),
+       # chain + shortcut: the layer1 block-0 shape only (Co 64, Ci2 64); x2 aligned; both geometries give Ho, Wo
+       (_X6_CDUAL, dict(Ci=48), -1), (_X6_CDUAL, dict(Ci=96), 0), (_X6_CDUAL, dict(Co=128), -1),
+       (_X6_CDUAL, dict(Co=32), -1), (_X6_CDUAL, dict(Ci2=128), -1), (_X6_CDUAL, dict(Ci2=32), -1),
+       (_X6_CDUAL, dict(Co2=64), 0), (_X6_CDUAL, dict(x2=0x40008), -1), (_X6_CDUAL, dict(H2=16), -1),
+       (_X6_CDUAL, dict(W2=16), -1), (_X6_CDUAL, dict(H2=16, W2=16, stride2=2), 0)]
+    # QUIRK: the stem entries reject N == 0, where the tensor entries answer 0
+    + [(e, v, -1) for e in (_X6_STEM, _X6_SPOOL) for v in (
+        dict(N=0), dict(N=-1), dict(x=None), dict(packed=None), dict(bias=None), dict(y=None), dict(H=0), dict(W=0),
+        dict(packed=0x20008))]
+    + [(_X6_STEM, v, -1) for v in (dict(Co=0), dict(Co=65), dict(Ho=7), dict(Wo=9), dict(H=18), dict(W=18))]
+    + [(_X6_SPOOL, v, -1) for v in (dict(Co=32), dict(Co=0), dict(Hp=7), dict(Wp=9), dict(H=36), dict(W=36),
+                                    dict(workspace=None), dict(workspace=0xA0008), dict(y=0x30008),
+                                    dict(workspace_bytes=0), dict(workspace_bytes=37 * 64 * 4 - 1))]
+)
+
+
+def _x6_call(lib, entry, changes, want):
+    args = dict(_X6_STEM_BASE.get(entry, _X6_BASE))
+    assert set(changes) <= set(_X6_ORDER[entry].split()), (entry, changes)
+    args.update(changes)
+    # only empty or rejected calls: nothing may reach a kernel
+    assert args["N"] <= 0 if entry in _X6_TENSOR else (want == -1 and changes), (entry, changes)
+    return getattr(lib, entry)(*[args[k] for k in _X6_ORDER[entry].split()])
+
+
+def test_conv_x6_argument_rules_without_gpu(lib):
+    """The split-bf16 convs' per-entry argument rules: every row is an accepted argument set (-> 0) or that set with
+    one rule broken (-> BEV_ERR_ARGS), answered before any HIP call (N = 0, or a rejected stem call).  The rows marked
+    QUIRK pin answers that are what they are, not what one would design.  No answer depends on the knobs that choose
+    among the k_conv_x6 / x6b / x6s instances."""
+    import bev_native as nat
+    assert len(_X6_ROWS) >= 80 and {e for e, _, _ in _X6_ROWS} == set(_X6_ORDER)
+    for knobs in ({}, dict(CONV_X6_TILE=1), dict(CONV_X6_TILE=2), dict(CONV_X6_KERNEL=1), dict(CONV_X6_NT=1)):
+        with nat.tuned(**knobs):
+            bad = [(knobs, e, c, want, got) for e, c, want in _X6_ROWS for got in [_x6_call(lib, e, c, want)]
+                   if got != want]
+        assert not bad, bad
+
+
 def test_tune_knobs_host_only(lib):
     """bev_tune: every knob returns its previous value, rejects out-of-range values and unknown knobs;
     no GPU involved (knobs are read at launch)."""

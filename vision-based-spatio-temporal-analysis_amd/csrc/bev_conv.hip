@@ -29,6 +29,7 @@
 
 #include "../../include/bev_mi355x.h"
 #include "bev_act.h"
+#include "bev_mfma.h"
 #include "bev_tune.h"
 
 namespace {
@@ -467,10 +468,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, float *lds, con
 // Buffer resources (base, byte size): the lane's row is in the VGPR offset (the part the range
 // check sees), so loads / stores of rows past the block's last one return 0 / are dropped; the
 // uniform column / k offset goes to the SGPR soffset.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t chain_rsrc(const float *p, int64_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)(uint32_t)bytes, 0x00020000);
-}
-
 // W2 fragments of half step t (k = 32 (t >> 1) + 16 hh + 8 (t & 1) + 0..7) for columns c0 + 32 j + r32.
 __device__ __forceinline__ void chain_load_b(__amdgpu_buffer_rsrc_t rw, int kp2, int voff, int c0, int t,
                                              f32x4 (&w)[2][2]) {
@@ -532,14 +529,14 @@ __device__ __forceinline__ void chain_epilogue(const ConvArgs &a, float *lds, co
     // this block's rows of res / y: [m0, min(m0 + BM, M)) x Co2 (ldy == Co2)
     const int64_t rows = (a.M - m0 < BM) ? a.M - m0 : BM;
     const int64_t base = m0 * a.Co2;
-    const __amdgpu_buffer_rsrc_t ry = chain_rsrc(a.y + base, rows * a.Co2 * 4);
-    const __amdgpu_buffer_rsrc_t rr = chain_rsrc(a.res ? a.res + base : a.y + base, rows * a.Co2 * 4);
-    const __amdgpu_buffer_rsrc_t rw = chain_rsrc(a.wp2, (int64_t)copad(a.Co2) * a.Kp2 * 4);
+    const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(a.y + base, rows * a.Co2 * 4);
+    const __amdgpu_buffer_rsrc_t rr = buffer_rsrc(a.res ? a.res + base : a.y + base, rows * a.Co2 * 4);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(a.wp2, (int64_t)copad(a.Co2) * a.Kp2 * 4);
     const int vw = (r32 * a.Kp2 + 16 * hh) * 4;                // lane part of a W2 address
     const int vo = ((wm * 32 + 4 * hh) * a.Co2 + r32) * 4;     // lane part of a res / y address
     // dual (downsample shortcut): K2 = [h2 | x2 at the lane row's strided pixel], x2 [N][H2][W2][Ci2]
     const int hs2 = a.x2 ? a.Ci2 / 16 : 0;
-    __amdgpu_buffer_rsrc_t rx = chain_rsrc(a.y, 0);
+    __amdgpu_buffer_rsrc_t rx = buffer_rsrc(a.y, 0);
     int vx = 0;
     if (a.x2) {
         int64_t m = m0 + wm * 32 + r32;
@@ -548,7 +545,7 @@ __device__ __forceinline__ void chain_epilogue(const ConvArgs &a, float *lds, co
         const int64_t q = m / a.Wo;
         const int oy = (int)(q % a.Ho);
         const int64_t n = q / a.Ho;
-        rx = chain_rsrc(a.x2, (int64_t)a.N * a.H2 * a.W2 * a.Ci2 * 4);
+        rx = buffer_rsrc(a.x2, (int64_t)a.N * a.H2 * a.W2 * a.Ci2 * 4);
         vx = (int)((((n * a.H2 + (int64_t)oy * a.stride2) * a.W2 + (int64_t)ox * a.stride2) * a.Ci2 + 16 * hh) * 4);
     }
     f32x4 wA[2][2], wB[2][2], xA[2], xB[2];
@@ -631,10 +628,7 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void k_conv(ConvArgs a) {
     // remapped so each XCD walks a contiguous run: the n_tiles blocks that read the same A rows are
     // dispatched together on one XCD and share its L2 instead of fetching A once per XCD.
     unsigned bid = blockIdx.x;
-    if (a.xcd) {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
+    if (a.xcd) bid = xcd_block(bid, gridDim.x);
     const int64_t m0 = (int64_t)(bid / n_tiles) * BM;
     const int n0 = (bid % n_tiles) * BN;
 
@@ -768,21 +762,6 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void k_conv(ConvArgs a) {
 // row r is stored at chunk c ^ ((r >> 1) & 7) (each lane fetches the logical chunk its slot holds),
 // which makes the fragment reads conflict-free: every 16-lane ds_read_b128 group covers 8 even and
 // 8 odd rows whose swizzles are all distinct.  Out-of-range taps and rows read a zero quad.
-__device__ __forceinline__ unsigned lds_base(const unsigned char *p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char *)p;
-}
-
-__device__ __forceinline__ void lds_dma16(const float *src, unsigned dst_any) {
-    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)dst_any);  // wave-uniform LDS address
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(dst)
-        : "memory");
-}
-
 template <int WM, int WN, int TM, int TN, int CHAIN>
 __global__ __launch_bounds__(256, (TM * TN > 2) ? 2 : 3) void k_conv_dma(ConvArgs a) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -801,10 +780,7 @@ __global__ __launch_bounds__(256, (TM * TN > 2) ? 2 : 3) void k_conv_dma(ConvArg
     const int wm = wave / WN, wn = wave % WN;
     const int n_tiles = (a.Co + BN - 1) / BN;
     unsigned bid = blockIdx.x;
-    if (a.xcd) {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
+    if (a.xcd) bid = xcd_block(bid, gridDim.x);
     const int64_t m0 = (int64_t)(bid / n_tiles) * BM;
     const int n0 = (bid % n_tiles) * BN;
 
@@ -836,7 +812,7 @@ __global__ __launch_bounds__(256, (TM * TN > 2) ? 2 : 3) void k_conv_dma(ConvArg
         const int c = (lane & 7) ^ ((row >> 1) & 7);
         bsrc[q] = a.wp + (int64_t)(n0 + row) * a.Kp + 4 * c;
     }
-    const unsigned lbase = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_base((const unsigned char *)lds));
+    const unsigned lbase = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr(lds));
     int ky = 0, kx = 0, ci0 = 0, kb = 0;
     auto issue = [&](int buf) {
         const unsigned d0 = lbase + (unsigned)(buf * STAGE * 4);
@@ -1082,17 +1058,8 @@ __global__ __launch_bounds__(256, 2) void k_stem(StemArgs a) {
     }
 }
 
-int g_num_cu = 0;
-
 int launch_stem(const float *x, int N, int H, int W, const float *packed, int Kp, const float *bias, int Co,
                 float *y, int Ho, int Wo, int relu, hipStream_t st) {
-    if (g_num_cu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                    hipSuccess || n <= 0)
-            n = 256;
-        g_num_cu = n;
-    }
     StemArgs a;
     a.x = x;
     a.wp = packed;
@@ -1109,9 +1076,9 @@ int launch_stem(const float *x, int N, int H, int W, const float *packed, int Kp
     a.nTx = (Wo + stem::TW - 1) / stem::TW;
     a.nTy = (Ho + stem::TH - 1) / stem::TH;
     a.ntiles = (int64_t)N * a.nTx * a.nTy;
-    const int64_t grid = a.ntiles < 2 * (int64_t)g_num_cu ? a.ntiles : 2 * (int64_t)g_num_cu;
+    const int64_t grid = a.ntiles < 2 * (int64_t)cu_count() ? a.ntiles : 2 * (int64_t)cu_count();
     hipLaunchKernelGGL(k_stem, dim3((unsigned)grid), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+    return last();
 }
 
 // NHWC max-pool (padding counts as -inf, as torch.nn.MaxPool2d); one float4
@@ -1171,8 +1138,6 @@ __global__ void k_transpose(const float *__restrict__ x, int R, int S, float *__
         if (r < R && s < S) yn[(int64_t)s * R + r] = tile[threadIdx.x][q];
     }
 }
-
-inline int last() { return (int)hipGetLastError(); }
 
 // BEV_TUNE_CONV_DMA: fast-loader layers stage their operands by LDS-DMA (k_conv_dma).  1 = on the 64-column
 // tiles only: r02l A/B over the ResNet-50 layers (7 x 1080p), LDS-DMA vs register staging: 128 x 64 and 64 x 64
@@ -1527,25 +1492,10 @@ ConvArgs conv_args(const float *x, const float *packed, const float *bias, const
 extern "C" {
 
 int bev_tune(int knob, int value) {
-    if (knob == BEV_TUNE_CONV_TILE) {
-        if (value < 0 || value > 4) return BEV_ERR_ARGS;
-        const int old = g_conv_tile;
-        g_conv_tile = value;
-        return old;
-    }
-    if (knob == BEV_TUNE_CONV_DMA) {
-        if (value < 0 || value > 2) return BEV_ERR_ARGS;
-        const int old = g_conv_dma;
-        g_conv_dma = value;
-        return old;
-    }
-    if (knob == BEV_TUNE_CONV_XCD || knob == BEV_TUNE_CONV_NBUF) {
-        int *slot = knob == BEV_TUNE_CONV_XCD ? &g_conv_xcd : &g_conv_nbuf;
-        if (value < 0 || value > (knob == BEV_TUNE_CONV_XCD ? 1 : 2)) return BEV_ERR_ARGS;
-        const int old = *slot;
-        *slot = value;
-        return old;
-    }
+    if (knob == BEV_TUNE_CONV_TILE) return bev::swap_knob(g_conv_tile, value, 4);
+    if (knob == BEV_TUNE_CONV_DMA) return bev::swap_knob(g_conv_dma, value, 2);
+    if (knob == BEV_TUNE_CONV_XCD) return bev::swap_knob(g_conv_xcd, value, 1);
+    if (knob == BEV_TUNE_CONV_NBUF) return bev::swap_knob(g_conv_nbuf, value, 2);
     if (knob == BEV_TUNE_WGRAD_MFMA) return bev::train_tune(knob, value);
     if (knob == BEV_TUNE_CONV_X6_TILE || knob == BEV_TUNE_CONV_X6_KERNEL || knob == BEV_TUNE_CONV_X6_NT)
         return bev::conv_x6_tune(knob, value);
@@ -1553,12 +1503,7 @@ int bev_tune(int knob, int value) {
     if (knob == BEV_TUNE_CONV_H16_BUF) return bev::conv_h16_buf_tune(value);
     if (knob == BEV_TUNE_DW_RUN) return bev::dw_tune(value);
     if (knob == BEV_TUNE_STEM3_STAGE) return bev::stem3_tune(value);
-    if (knob == BEV_TUNE_CONV_PW_SMALL) {
-        if (value < 0 || value > 4) return BEV_ERR_ARGS;
-        const int old = g_conv_pw_small;
-        g_conv_pw_small = value;
-        return old;
-    }
+    if (knob == BEV_TUNE_CONV_PW_SMALL) return bev::swap_knob(g_conv_pw_small, value, 4);
     return bev::warp_tune(knob, value);
 }
 
@@ -1616,7 +1561,7 @@ static int conv2d_impl(const float *x, int in_nchw, int N, int H, int W, int Ci,
     if (!x || !packed || !y || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 || KW <= 0 ||
         stride <= 0 || pad < 0 || relu < 0 || relu > 2 || dil <= 0 || ldy < Co || (residual && ldy != Co))
         return BEV_ERR_ARGS;
-    if (Ho != (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1 || Wo != (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1 ||
+    if (Ho != conv_out(H, pad, dil, KH, stride) || Wo != conv_out(W, pad, dil, KW, stride) ||
         Ho <= 0 || Wo <= 0)
         return BEV_ERR_ARGS;
     if (N == 0) return 0;
@@ -1644,7 +1589,7 @@ int bev_conv2d_dual_f32(const float *x, int N, int Ho, int Wo, int Ci, const flo
         stride2 <= 0 || Co <= 0)
         return BEV_ERR_ARGS;
     if (Ci % BK != 0 || Ci2 % BK != 0) return BEV_ERR_ARGS;
-    if (Ho != (H2 - 1) / stride2 + 1 || Wo != (W2 - 1) / stride2 + 1) return BEV_ERR_ARGS;
+    if (Ho != conv_out(H2, 0, 1, 1, stride2) || Wo != conv_out(W2, 0, 1, 1, stride2)) return BEV_ERR_ARGS;
     if (N == 0) return 0;
     ConvArgs a = conv_args(x, packed, bias, nullptr, y, N, Ho, Wo, Ci, Co, 1, 1, 1, 0, 1, Ho, Wo, relu, Co);
     a.K = Ci + Ci2;
@@ -1662,7 +1607,7 @@ static int chain_impl(const float *x, int N, int H, int W, int Ci, const float *
     if (dual) {
         if (!x2 || Ci2 <= 0 || Ci2 % BK != 0 || H2 <= 0 || W2 <= 0 || stride2 <= 0 || ((uintptr_t)x2 & 15) != 0)
             return BEV_ERR_ARGS;
-        if (Ho != (H2 - 1) / stride2 + 1 || Wo != (W2 - 1) / stride2 + 1) return BEV_ERR_ARGS;
+        if (Ho != conv_out(H2, 0, 1, 1, stride2) || Wo != conv_out(W2, 0, 1, 1, stride2)) return BEV_ERR_ARGS;
         if ((int64_t)N * H2 * W2 * Ci2 * 4 > (int64_t)0xffffffff) return BEV_ERR_ARGS;  // 32-bit buffer offsets
     }
     if (!x || !packed || !packed2 || !y || N < 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
@@ -1671,7 +1616,7 @@ static int chain_impl(const float *x, int N, int H, int W, int Ci, const float *
     if (Ci % BK != 0 || (Co != 64 && Co != 128) || Co2 <= 0 || Co2 % 128 != 0 || ((uintptr_t)x & 15) != 0 ||
         (((uintptr_t)packed | (uintptr_t)packed2) & 15) != 0)
         return BEV_ERR_ARGS;
-    if (Ho != (H + 2 * pad - KH) / stride + 1 || Wo != (W + 2 * pad - KW) / stride + 1 || Ho <= 0 || Wo <= 0)
+    if (Ho != conv_out(H, pad, 1, KH, stride) || Wo != conv_out(W, pad, 1, KW, stride) || Ho <= 0 || Wo <= 0)
         return BEV_ERR_ARGS;
     if (N == 0) return 0;
     ConvArgs a = conv_args(x, packed, bias, residual, y, N, H, W, Ci, Co, KH, KW, stride, pad, 1, Ho, Wo, relu, Co2);
@@ -1733,7 +1678,7 @@ __global__ __launch_bounds__(256) void k_maxpool_rows(const float4 *__restrict__
 int bev_maxpool2d_nhwc_f32(const float *x, int N, int H, int W, int C, int k, int stride, int pad, float *y, int Ho,
                            int Wo, void *stream) {
     if (!x || !y || N < 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || stride <= 0 || pad < 0) return BEV_ERR_ARGS;
-    if (Ho != (H + 2 * pad - k) / stride + 1 || Wo != (W + 2 * pad - k) / stride + 1) return BEV_ERR_ARGS;
+    if (Ho != conv_out(H, pad, 1, k, stride) || Wo != conv_out(W, pad, 1, k, stride)) return BEV_ERR_ARGS;
     const bool vec = (C % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0);
     const int64_t total = (int64_t)N * Ho * Wo * (vec ? C / 4 : C);
     if (total == 0) return 0;

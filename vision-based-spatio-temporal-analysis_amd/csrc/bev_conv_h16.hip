@@ -21,6 +21,8 @@
 
 #include "../../include/bev_mi355x.h"
 #include "bev_act.h"
+#include "bev_mfma.h"
+#include "bev_tune.h"
 
 namespace {
 
@@ -85,11 +87,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16(ConvH a) {
     const int wm = wave >> 1, wn = wave & 1;
     const int ntn = (a.Co + HBN - 1) / HBN;
     const int64_t ntm = (a.M + HBM - 1) / HBM;
-    unsigned bid = blockIdx.x;
-    {  // XCD-aware order: consecutive blocks (the N tiles of one M block) on one XCD
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);
     const int64_t mt = bid / (unsigned)ntn;
     const int nt = (int)(bid % (unsigned)ntn);
     if (mt >= ntm) return;
@@ -349,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
     const int ntn = (a.Co + BN - 1) / BN;
     const int64_t ntm = (a.M + HBM - 1) / HBM;
     unsigned bid = blockIdx.x;
-    {
+    {  // xcd_block() written out: through the helper the four <true, *, *, false, true> instances lose 3 instructions
         const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
         bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
     }
@@ -403,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h16b(ConvH a) {
     static_assert(!BUF || HIN, "buffer staging: fp16 operand");
     __amdgpu_buffer_rsrc_t rsx, rsw;
     int xrb[NQ], wvo[NBU];  // BUF: byte offsets of row q's (0, 0) tap piece / of weight load u at K step 0
-    if constexpr (BUF) {
+    if constexpr (BUF) {  // buffer_rsrc() written out: through the helper 6 of the 10 BUF instances change
         rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(a.xh), 0,
                                                 (int)((int64_t)a.N * a.H * a.W * a.Ci * 2), 0x00020000);
         rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(a.wp), 0,
@@ -663,11 +661,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_h16b(const float *__restrict__
                                                         int K, int stride, int pad, int dil, int64_t mchunk, int ctiles,
                                                         int ntiles, float *__restrict__ dW) {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2][2 * WT * WROW2];
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);
     const int tile = (int)(bid % (unsigned)ntiles);
     const int64_t split = bid / (unsigned)ntiles;
     const int co0 = (tile % ctiles) * WT, k0 = (tile / ctiles) * WT;
@@ -847,11 +841,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_h16c(const float *__restrict__
     __shared__ __attribute__((aligned(16))) _Float16 lds[2][2 * IMG];
     const _Float16 *dz = (const _Float16 *)dzv;  // DH: fp16 gradient; else fp32 (dzf), rounded while staging
     const float *dzf = (const float *)dzv;
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);
     const int tile = (int)(bid % (unsigned)ntiles);
     const int split = (int)(bid / (unsigned)ntiles);
     const int co0 = (tile % ctiles) * WT, k0 = (tile / ctiles) * WT;
@@ -1106,23 +1096,17 @@ int conv_h16(const ConvIo &io, int N, int H, int W, int Ci, const uint16_t *pack
                      copad_h(Co) * (int64_t)a.Kp * 2 < ((int64_t)1 << 31) - 16;
     void (*kern)(ConvH) = wide ? conv_h16b_kernel(io.x_half, n64, buf, io.y_half, aff) : k_conv_h16;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    return last();
 }
 
 }  // namespace
 
 namespace bev {
 int conv_h16_tune(int value) {
-    if (value < 0 || value > 3) return BEV_ERR_ARGS;
-    const int old = g_h16_kernel;
-    g_h16_kernel = value;
-    return old;
+    return swap_knob(g_h16_kernel, value, 3);
 }
 int conv_h16_buf_tune(int value) {
-    if (value < 0 || value > 1) return BEV_ERR_ARGS;
-    const int old = g_h16_buf;
-    g_h16_buf = value;
-    return old;
+    return swap_knob(g_h16_buf, value, 1);
 }
 }  // namespace bev
 
@@ -1143,7 +1127,7 @@ int bev_conv_wgrad_h16_ex_f32(const void *xv, int x_half, int N, int H, int W, i
     const int K = KH * KW * Ci;
     const int64_t M = (int64_t)N * Ho * Wo;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dW, 0, (size_t)Co * K * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
+    if (hipMemsetAsync(dW, 0, (size_t)Co * K * sizeof(float), st) != hipSuccess) return last();
     if (M == 0) return 0;
     const int ct = (Co + WT - 1) / WT, kt = (K + WT - 1) / WT, nt = ct * kt;
     int64_t sp = 1024 / nt + 1;  // >= ~1024 workgroups
@@ -1166,7 +1150,7 @@ int bev_conv_wgrad_h16_ex_f32(const void *xv, int x_half, int N, int H, int W, i
         hipLaunchKernelGGL(kern, dim3((unsigned)(sp * nt)), dim3(256), 0, st, x, dz, N, H, W, Ci, Ho, Wo, Co, KW, K,
                            stride, pad, dilation, mc, ct, nt, dW);
     }
-    return (int)hipGetLastError();
+    return last();
 }
 
 int bev_conv_wgrad_h16_f32(const float *x, int N, int H, int W, int Ci, const float *dz, int Ho, int Wo, int Co,
@@ -1184,7 +1168,7 @@ int bev_conv_pack_weights_h16(const float *w, int Co, int Ci, int KH, int KW, ui
     const int64_t Kp = kpad_h(Ci * KH * KW), Cop = copad_h(Co), n = Kp * Cop;
     hipLaunchKernelGGL(k_pack_h16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, Co, Ci, KH,
                        KW, Kp, Cop, (_Float16 *)packed);
-    return (int)hipGetLastError();
+    return last();
 }
 
 int bev_conv2d_h16_ex_f32(const void *x, int x_half, int N, int H, int W, int Ci, const uint16_t *packed,

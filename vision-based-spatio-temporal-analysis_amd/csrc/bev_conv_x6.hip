@@ -14,11 +14,9 @@
 // keep a NaN, bev_act.h).  Measured on an MI355X: operands scaled by 2^-30 .. 2^30 each (outputs 2^-60 .. 2^60 times
 // unit scale) give bit-identical scaled outputs; at 2^-50 x 2^-50 (outputs ~2^-100, the low planes' products fp32
 // subnormal) and 2^50 x 2^50 the result still meets the 1e-5 max|ref| float64 bar (5.5e-7 seen, as at unit scale).
-// A product a*b is then the sum of nine bf16 x bf16
-// products, each EXACT in fp32; the six kept here are those larger than 2^-27 |a b|:
-//     hh + hm + mh + hl + lh + mm          (dropped: ml + lm + ll <= 2^-26 |a b|, below fp32's 2^-24 rounding)
-// and all of them accumulate into the fp32 MFMA accumulator.  The result is an fp32 GEMM whose per-product error
-// (<= 2^-26 relative) is below the fp32 rounding of the running sum it is added to, so it is exactly as accurate as
+// A product a*b is then the sum of nine bf16 x bf16 products, each EXACT in fp32; six of them are kept (x6_dot below:
+// which, in what order, and why the other three are dropped) and all of them accumulate into the fp32 MFMA
+// accumulator.  The result is an fp32 GEMM whose per-product error (<= 2^-26 relative) is below the fp32 rounding of the running sum it is added to, so it is exactly as accurate as
 // the exact-f32 MFMA path (tests/test_conv_x6_gpu.py measures both against float64), at 6 bf16 MFMAs per 16-deep
 // k slice instead of 8 fp32 32x32x2 MFMAs per 16: v_mfma_f32_32x32x16_bf16 is 32 cycles, v_mfma_f32_32x32x2_f32
 // 64 (MI355X_MICROARCH.md), so the matrix-core time per output falls from 512 to 192 cycles (2.67x).
@@ -39,6 +37,8 @@
 
 #include "../../include/bev_mi355x.h"
 #include "bev_act.h"
+#include "bev_mfma.h"
+#include "bev_tune.h"
 
 namespace {
 
@@ -63,6 +63,21 @@ __device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l)
     const float r = v - (float)h;
     m = (__bf16)r;
     l = (__bf16)(r - (float)m);
+}
+
+// The split product of one 16-deep k slice, c += A B for a 32 x 32 tile: six v_mfma_f32_32x32x16_bf16 over the planes
+// a[p], b[p] (p = 0, 1, 2: h, m, l), in the order
+//     hh + hm + mh + hl + lh + mm          (dropped: ml + lm + ll <= 2^-26 |a b|, below fp32's 2^-24 rounding)
+// -- the six of the nine plane products that are larger than 2^-27 |a b|.  Every kernel of this file forms its
+// products here and nowhere else: the one order is what makes the chain kernels bit-identical to the two launches they
+// replace, and k_conv_x6s (pre-split operand) to k_conv_x6 / k_conv_x6b (fp32 operand split while staging).
+__device__ __forceinline__ void x6_dot(f32x16 &c, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
 }
 
 // OIHW fp32 -> split panel in MFMA B-fragment order: [Co_pad / 32][K_pad / 16][plane h, m, l][lane 64][8] bf16,
@@ -92,7 +107,7 @@ __global__ void k_pack_x6(const float *__restrict__ w, int Co, int Ci, int KH, i
     out[frag_index(n, k, 2, S)] = l;
 }
 
-struct ConvX {  // conv_x6_args fills the geometry; an entry point sets what is particular to it over these defaults
+struct ConvX {  // filled by conv_x6()
     const float *__restrict__ x = nullptr;
     const __bf16 *__restrict__ wp = nullptr;
     const float *__restrict__ bias = nullptr;
@@ -256,11 +271,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (SGPR)
     const int wm = wave / WN, wn = wave % WN;
     const int n_tiles = (a.Co + BN - 1) / BN;
-    unsigned bid = blockIdx.x;
-    {  // XCD-aware order: the n_tiles blocks reading the same A rows run on one XCD (shared L2)
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);  // the n_tiles blocks of the same A rows on one XCD
     const int64_t m0 = (int64_t)(bid / n_tiles) * BM;
     const int n0 = (bid % n_tiles) * BN;
 
@@ -358,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
         _Pragma("unroll") for (int i = 0; i < BQ; ++i) *(bpiece *)(Bs + bdst[i]) = VB[i];                \
     } while (0)
     const int r32 = lane & 31, h = lane >> 5;
-    // one 16-deep k slice: 6 MFMAs per (A tile, B tile) pair (hh, hm, mh, hl, lh, mm)
+    // one 16-deep k slice: x6_dot per (A tile, B tile) pair
 #define X6_MFMA(BUF)                                                                                       \
     do {                                                                                                   \
         const __bf16 *As = lds + (BUF) * STAGE;                                                            \
@@ -371,14 +382,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
             _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                  \
                 fb[j][p] = *(const bf16x8 *)(Bs + p * BPL + (wn * TN * 32 + j * 32 + r32) * XROW + 8 * h); \
         _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                     \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                               \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], acc[i][j], 0, 0, 0); \
-            }                                                                                              \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                 \
+                x6_dot(acc[i][j], fa[i], fb[j]);                                                           \
     } while (0)
 
     const int nk = a.Kp / XBK;
@@ -430,25 +435,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
 // fragment-order panel, one step ahead); a block's residual is loaded one block ahead; residual and output are
 // addressed by buffer instructions (row in the VGPR offset, so rows past M read 0 / are dropped).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t x6_rsrc(const void *p, int64_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)(uint32_t)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void *p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-
-__device__ __forceinline__ void dma16(const void *src, unsigned dst_any) {
-    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)dst_any);  // wave-uniform LDS address
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(dst)
-        : "memory");
-}
-
 // this wave's older vector-memory operations have completed except the newest N (vmcnt retires in issue order), its
 // LDS reads have returned, and every wave of the workgroup has got here
 template <int N>
@@ -507,7 +493,8 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
     // bias2 ([16]) and residual ([0..15], HR) of the wave's block at column c0.  !live (the look-ahead of the last
     // block): the same instructions on empty buffers -- no memory access, and the loop's vmcnt counts hold as they are
     auto res_load = [&](auto hr, int c0, float(&rv)[17], bool live) {
-        const __amdgpu_buffer_rsrc_t rr = x6_rsrc(resp, live ? resb : 0), rb = x6_rsrc(biasp, live ? biasb : 0);
+        const __amdgpu_buffer_rsrc_t rr = buffer_rsrc(resp, live ? resb : 0);
+        const __amdgpu_buffer_rsrc_t rb = buffer_rsrc(biasp, live ? biasb : 0);
         rv[16] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, r32 * 4, c0 * 4, 0));
         if constexpr (decltype(hr)::value) {
 #pragma unroll
@@ -524,7 +511,8 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
 #pragma unroll
         for (int i = 0; i < PW; ++i) {
             const int q = wave + 4 * i, cbl = q / 12, r = q % 12;
-            dma16(wsrc + (((int64_t)(g * WPB + cbl) * ST + 4 * u) * 3 + r) * 512, lbase + sbo + (unsigned)(q * 1024));
+            lds_dma16(wsrc + (((int64_t)(g * WPB + cbl) * ST + 4 * u) * 3 + r) * 512,
+                      lbase + sbo + (unsigned)(q * 1024));
         }
     };
     // first block's residual: requested before the h2 staging, so its latency overlaps it
@@ -583,7 +571,7 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
     }
     // everything this wave has issued so far is complete: the counted waits of the loop start from an empty queue
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const __amdgpu_buffer_rsrc_t ry = x6_rsrc(a.y + base, rows * a.Co2 * 4);
+    const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(a.y + base, rows * a.Co2 * 4);
     // one column block: rc = its bias2 / residual (loaded during the previous block), rn = the next block's
     auto block = [&](auto hr, auto a2, int g, float(&rc)[17], float(&rn)[17]) {
         constexpr bool HAS_RES = decltype(hr)::value;
@@ -612,12 +600,7 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
                 bf16x8 fb[3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p) fb[p] = *(const bf16x8 *)(Bs + (sl * 3 + p) * 512);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][0], fb[0], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][0], fb[1], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][1], fb[0], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][0], fb[2], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][2], fb[0], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][1], fb[1], acc2, 0, 0, 0);
+                x6_dot(acc2, fa[t], fb);
             }
         }
         const float bj = rc[16];
@@ -675,11 +658,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (SGPR)
     const int wm = wave / WN, wn = wave % WN;
     const int n_tiles = (a.Co + BN - 1) / BN;
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);  // the n_tiles blocks of the same A rows on one XCD
     const int64_t m0 = (int64_t)(bid / n_tiles) * BM;
     const int n0 = (bid % n_tiles) * BN;
 
@@ -782,14 +761,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
             _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                  \
                 fa[i][p] = *(const bf16x8 *)(AS + p * APL + (wm * TM * 32 + i * 32 + r32) * YROW + 16 * (KK) + 8 * h); \
         _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                     \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                               \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], BC[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], BC[j][1], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], BC[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], BC[j][2], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], BC[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], BC[j][1], acc[i][j], 0, 0, 0); \
-            }                                                                                              \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                 \
+                x6_dot(acc[i][j], fa[i], BC[j]);                                                           \
     } while (0)
     // MFMAs of K step KS from LDS buffer BUF: slice 2 KS (B in bs0), slice 2 KS + 1 (B in bs1, loaded by the caller
     // BEFORE the step's A prefetch), the next step's slice 0 loaded into bs0 in between.  Order matters: vmcnt
@@ -895,11 +868,7 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (SGPR)
     const int wm = wave / WN, wn = wave % WN;
     const int n_tiles = (a.Co + BN - 1) / BN;
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);  // the n_tiles blocks of the same A rows on one XCD
     const int64_t m0 = (int64_t)(bid / n_tiles) * BM;
     const int n0 = (bid % n_tiles) * BN;
 
@@ -933,7 +902,7 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
 #pragma unroll
             for (int i = 0; i < BPW; ++i) {
                 const int q = wave + 4 * i, cbl = q / 6, r = q % 6;
-                dma16(bsrc + ((int64_t)cbl * S + 2 * kstep + r / 3) * 1536 + (r % 3) * 512,
+                lds_dma16(bsrc + ((int64_t)cbl * S + 2 * kstep + r / 3) * 1536 + (r % 3) * 512,
                       db + (unsigned)(q * 1024));
             }
             ++kstep;
@@ -947,7 +916,7 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
             const __bf16 *src = a.xs + abase[g] + toff;
 #pragma unroll
             for (int p = 0; p < 3; ++p)
-                dma16(in ? (const void *)(src + p * a.xps) : (const void *)g_xzero4,
+                lds_dma16(in ? (const void *)(src + p * a.xps) : (const void *)g_xzero4,
                       d0 + (unsigned)(p * APL * 2 + g * 1024));
         }
         ci0 += YBK;
@@ -960,8 +929,7 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
         }
     };
 
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<__bf16 *>(a.wp), 0, (int)(uint32_t)(copad_x(a.Co) / 32 * (int64_t)S * 3072), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(a.wp, copad_x(a.Co) / 32 * (int64_t)S * 3072);
     const int cb0 = (n0 + wn * TN * 32) >> 5;
     const int vl = lane * 16;
     bf16x8 bs0[TN][3], bs1[TN][3];
@@ -984,14 +952,8 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
                 fa[i][p] = *(const bf16x8 *)(AS + p * APL + R * 32 + ph * 8);                              \
         }                                                                                                  \
         _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                     \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                               \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], BC[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], BC[j][1], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], BC[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], BC[j][2], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], BC[j][0], acc[i][j], 0, 0, 0); \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], BC[j][1], acc[i][j], 0, 0, 0); \
-            }                                                                                              \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                 \
+                x6_dot(acc[i][j], fa[i], BC[j]);                                                           \
     } while (0)
 
     f32x16 acc[TM][TN];
@@ -1057,54 +1019,108 @@ __global__ void k_split3(const float *__restrict__ x, int64_t n, __bf16 *__restr
     out[t + 2 * n] = l;
 }
 
-// one workgroup per BM x BN output tile; `kernel` = the k_conv_x6 / k_conv_x6b / k_conv_x6s instance with that tile
-// (BM = WM TM 32, BN = WN TN 32)
-template <int BM, int BN>
-int launch_x6(void (*kernel)(ConvX), const ConvX &a, hipStream_t st) {
-    const int64_t blocks = ((a.M + BM - 1) / BM) * ((a.Co + BN - 1) / BN);
-    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-}
-
-// The geometry every entry point passes on; what is particular to one (x2 ..., xs / xps, ys / yps, the chained
-// conv's wp2 / bias2 / Co2 / act2, a dual K) it sets itself.
-ConvX conv_x6_args(const float *x, const uint16_t *packed, const float *bias, const float *res, float *y, int N, int H,
-                   int W, int Ci, int Co, int KH, int KW, int stride, int pad, int dil, int Ho, int Wo, int act,
-                   int ldy) {
-    ConvX a;
-    a.x = x, a.wp = (const __bf16 *)packed, a.bias = bias, a.res = res, a.y = y;
-    a.N = N, a.H = H, a.W = W, a.Ci = Ci, a.Co = Co, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
-    a.dil = dil, a.Ho = Ho, a.Wo = Wo, a.act = act, a.ldy = ldy;
-    a.Kp = (int)kpad_x(Ci * KH * KW);
-    a.M = (int64_t)N * Ho * Wo;
-    return a;
-}
-
 int g_x6_tile = 0;  // 0 automatic, 1 = 128 x 128, 2 = 128 x 64
 int g_x6_nt = 0;    // BEV_TUNE_CONV_X6_NT: 1 = non-temporal activation loads in the 32-deep kernels
 int g_x6_kernel = 0;  // 0 automatic (k_conv_x6b wherever it applies), 1 = k_conv_x6 (16-deep K steps) everywhere
 
-template <bool DUAL>
-int dispatch_x6(const ConvX &a0, hipStream_t st) {
-    ConvX a = a0;
+// one workgroup per BM x BN output tile; `kernel` = the k_conv_x6 / k_conv_x6b / k_conv_x6s instance with that tile
+// (BM = WM TM 32, BN = WN TN 32)
+int launch_x6(void (*kernel)(ConvX), int BM, int BN, const ConvX &a, hipStream_t st) {
+    const int64_t blocks = ((a.M + BM - 1) / BM) * ((a.Co + BN - 1) / BN);
+    if (blocks >= ((int64_t)1 << 31)) return BEV_ERR_ARGS;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    return last();
+}
+
+// What a tensor entry point asks for.  An entry fills what it has and leaves the rest at these defaults, under which
+// the rules of conv_x6() that do not concern it hold by themselves: a null pointer is aligned, and the dual form's
+// first operand is the 1x1 / stride 1 conv over x [N][Ho][Wo][Ci] that needs no geometry check of its own.
+enum X6Form { X6_PLAIN, X6_DUAL, X6_CHAIN, X6_CHAIN_DUAL };
+struct X6Call {
+    X6Form form;
+    // the conv (of a chain: the first, conv2 of the bottleneck): exactly one of x (fp32) and xs (pre-split planes)
+    const float *x = nullptr;
+    const uint16_t *xs = nullptr, *packed = nullptr;
+    const float *bias = nullptr, *res = nullptr;
+    float *y = nullptr;
+    uint16_t *ys = nullptr;  // plain only: split output planes in place of y
+    int N = 0, H = 0, W = 0, Ci = 0, Co = 0, KH = 1, KW = 1, stride = 1, pad = 0, dil = 1, act = 0, ldy = 0, Ho = 0,
+        Wo = 0;
+    // second operand (dual, chain-dual): x2 [N][H2][W2][Ci2] read at (oy stride2, ox stride2)
+    const float *x2 = nullptr;
+    int H2 = 0, W2 = 0, Ci2 = 0, stride2 = 0;
+    // second conv (chain, chain-dual): 1x1 over the first one's Co channels; res and y belong to it
+    const uint16_t *packed2 = nullptr;
+    const float *bias2 = nullptr;
+    int Co2 = 0, act2 = 0;
+};
+
+// The one host path of the split convs: validates, fills ConvX, picks the kernel instance.
+int conv_x6(const X6Call &c, hipStream_t st) {
+    const bool chain = c.form == X6_CHAIN || c.form == X6_CHAIN_DUAL;
+    const bool second = c.form == X6_DUAL || c.form == X6_CHAIN_DUAL;  // has x2
+    if ((!c.x == !c.xs) || !c.packed || (!c.y == !c.ys) || c.N < 0 || c.H <= 0 || c.W <= 0 || c.Co <= 0 || c.KH <= 0 ||
+        c.KW <= 0 || c.stride <= 0 || c.pad < 0 || c.dil <= 0 || c.act < 0 || c.act > 2)
+        return BEV_ERR_ARGS;
+    // one tap and 16 channels per K step; 32 for a pre-split operand and in the chains (k_conv_x6b / k_conv_x6s only).
+    // The chains check no more of Ci than this.
+    if ((!chain && c.Ci <= 0) || c.Ci % (chain || c.xs ? YBK : XBK) != 0) return BEV_ERR_ARGS;
+    if (second && (!c.x2 || c.H2 <= 0 || c.W2 <= 0 || c.Ci2 <= 0 || c.stride2 <= 0)) return BEV_ERR_ARGS;
+    if (c.form == X6_DUAL && c.Ci2 % XBK != 0) return BEV_ERR_ARGS;
+    if (chain && (!c.packed2 || c.act2 < 0 || c.act2 > 2 || c.Co2 <= 0 || c.Co2 % 64 != 0)) return BEV_ERR_ARGS;
+    // the chain epilogue holds all of h2: 64 or 128 channels; with the shortcut operand the layer1 block-0 shape only
+    // (64-channel h2 and a 64-channel x2, 4 slices kept in registers)
+    if (c.form == X6_CHAIN && c.Co != 64 && c.Co != 128) return BEV_ERR_ARGS;
+    if (c.form == X6_CHAIN_DUAL && (c.Co != 64 || c.Ci2 != 64)) return BEV_ERR_ARGS;
+    if (c.Ho != conv_out(c.H, c.pad, c.dil, c.KH, c.stride) || c.Wo != conv_out(c.W, c.pad, c.dil, c.KW, c.stride) ||
+        c.Ho <= 0 || c.Wo <= 0)
+        return BEV_ERR_ARGS;
+    if (second && (c.Ho != conv_out(c.H2, 0, 1, 1, c.stride2) || c.Wo != conv_out(c.W2, 0, 1, 1, c.stride2)))
+        return BEV_ERR_ARGS;
+    if ((((uintptr_t)c.x | (uintptr_t)c.xs | (uintptr_t)c.x2 | (uintptr_t)c.packed | (uintptr_t)c.packed2) & 15) != 0)
+        return BEV_ERR_ARGS;
+    // y rows of ldy >= Co floats; dense for a residual and for split output (a chain's y: dense rows of Co2)
+    if (!chain && (c.ldy < c.Co || (c.res && c.ldy != c.Co))) return BEV_ERR_ARGS;
+    if (c.ys && (c.ldy != c.Co || c.Co % 4 != 0 || ((uintptr_t)c.ys & 7) != 0)) return BEV_ERR_ARGS;
+    if (c.N == 0) return 0;
+    // two waves share each 32-row band of the 64-row tile (checked behind the empty call's answer: test_capi.py pins it)
+    if (c.form == X6_CHAIN && c.Co != 64 && c.Co2 % 128 != 0) return BEV_ERR_ARGS;
+
+    ConvX a;
+    a.x = c.x, a.wp = (const __bf16 *)c.packed, a.bias = c.bias, a.res = c.res, a.y = c.y;
+    a.N = c.N, a.H = c.H, a.W = c.W, a.Ci = c.Ci, a.Co = c.Co, a.KH = c.KH, a.KW = c.KW, a.stride = c.stride;
+    a.pad = c.pad, a.dil = c.dil, a.Ho = c.Ho, a.Wo = c.Wo, a.act = c.act, a.ldy = chain ? c.Co2 : c.ldy;
+    a.Kp = (int)kpad_x(c.form == X6_DUAL ? c.Ci + c.Ci2 : c.Ci * c.KH * c.KW);  // dual: one GEMM over K = [x | x2]
+    a.M = (int64_t)c.N * c.Ho * c.Wo;
+    a.x2 = c.x2, a.Ci2 = c.Ci2, a.H2 = c.H2, a.W2 = c.W2, a.stride2 = c.stride2;
+    a.xs = (const __bf16 *)c.xs, a.ys = (__bf16 *)c.ys;
+    a.xps = (int64_t)c.N * c.H * c.W * c.Ci, a.yps = a.M * c.Co;
+    a.wp2 = (const __bf16 *)c.packed2, a.bias2 = c.bias2, a.Co2 = c.Co2, a.act2 = c.act2;
+
+    // The chains.  A pre-split operand (conv1 handed over its output split) is staged by LDS-DMA (k_conv_x6s), same K
+    // order.  h2 of 128 channels: the 64 x 128 tile (h2 planes 52 KiB of LDS).
+    if (c.form == X6_CHAIN_DUAL)
+        return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 2> : k_conv_x6b<4, 1, 1, 2, false, 2>, 128, 64, a, st);
+    if (c.form == X6_CHAIN && c.Co == 64)
+        return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 1> : k_conv_x6b<4, 1, 1, 2, false, 1>, 128, 64, a, st);
+    if (c.form == X6_CHAIN)
+        return launch_x6(c.xs ? k_conv_x6s<2, 2, 1, 2, 1> : k_conv_x6b<2, 2, 1, 2, false, 1>, 64, 128, a, st);
+    // One conv (plain, dual): the 128 x 64 tile (t == 2) up to 64 output channels, else 128 x 128
+    const bool dual = c.form == X6_DUAL;
     a.nta = g_x6_nt;
     const int t = g_x6_tile ? g_x6_tile : (a.Co <= 64 ? 2 : 1);
-    if (!DUAL && a.xs) {
-        if (t == 2) return launch_x6<128, 64>(k_conv_x6s<4, 1, 1, 2>, a, st);
-        return launch_x6<128, 128>(k_conv_x6s<2, 2, 2, 2>, a, st);
-    }
+    if (a.xs) return t == 2 ? launch_x6(k_conv_x6s<4, 1, 1, 2>, 128, 64, a, st)
+                            : launch_x6(k_conv_x6s<2, 2, 2, 2>, 128, 128, a, st);
     // automatic = the 32-deep-step kernel wherever it applies: single 1x1 layers measured faster on the 16-deep
     // kernel in isolation, but the ResNet-50 encoder (two stream groups) is fastest with the 32-deep kernel
     // everywhere (r03 tools/trunk_ab.py: 16.24 ms vs 16.34 with 1x1 / dual layers on the 16-deep one, 16.43 all)
-    const bool wide = a.Ci % YBK == 0 && (!DUAL || a.Ci2 % YBK == 0) && g_x6_kernel != 1;
-    if (wide) {
-        if (t == 2 && !DUAL && a.nta) return launch_x6<128, 64>(k_conv_x6b<4, 1, 1, 2, false, 0, true>, a, st);
-        if (t == 2) return launch_x6<128, 64>(k_conv_x6b<4, 1, 1, 2, DUAL>, a, st);
-        return launch_x6<128, 128>(k_conv_x6b<2, 2, 2, 2, DUAL>, a, st);
-    }
-    if (t == 2) return launch_x6<128, 64>(k_conv_x6<4, 1, 1, 2, DUAL>, a, st);
-    return launch_x6<128, 128>(k_conv_x6<2, 2, 2, 2, DUAL>, a, st);
+    const bool wide = a.Ci % YBK == 0 && (!dual || a.Ci2 % YBK == 0) && g_x6_kernel != 1;
+    if (wide && t == 2 && !dual && a.nta) return launch_x6(k_conv_x6b<4, 1, 1, 2, false, 0, true>, 128, 64, a, st);
+    if (wide && t == 2)
+        return launch_x6(dual ? k_conv_x6b<4, 1, 1, 2, true> : k_conv_x6b<4, 1, 1, 2, false>, 128, 64, a, st);
+    if (wide) return launch_x6(dual ? k_conv_x6b<2, 2, 2, 2, true> : k_conv_x6b<2, 2, 2, 2, false>, 128, 128, a, st);
+    if (t == 2) return launch_x6(dual ? k_conv_x6<4, 1, 1, 2, true> : k_conv_x6<4, 1, 1, 2, false>, 128, 64, a, st);
+    return launch_x6(dual ? k_conv_x6<2, 2, 2, 2, true> : k_conv_x6<2, 2, 2, 2, false>, 128, 128, a, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1291,15 +1307,7 @@ __global__ __launch_bounds__(stem6::NTHR, 1) void k_stem_x6(StemX6Args a) {
                     fa[p] = __builtin_bit_cast(bf16x8, (u32x4){q[0], q[1], q[2], q[3] & 0xffffu});
                 }
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    f32x16 &c = acc[mt][j];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[j][1], c, 0, 0, 0);
-                }
+                for (int j = 0; j < 2; ++j) x6_dot(acc[mt][j], fa, fb[j]);
             }
             __builtin_amdgcn_sched_barrier(0);  // one slice of operands live at a time
         }
@@ -1494,15 +1502,27 @@ __global__ __launch_bounds__(256) void k_stem_pool_seams(float *__restrict__ y, 
     *yp = m;
 }
 
+// The stem kernels' arguments without the pooled form's edge buffers; one persistent workgroup per CU at most.
+StemX6Args stem_x6_args(const float *x, int N, int H, int W, const uint16_t *packed, const float *bias, int Co,
+                        int relu, float *y, int Ho, int Wo) {
+    StemX6Args a;
+    a.x = x, a.wp = (const __bf16 *)packed, a.bias = bias, a.y = y;
+    a.H = H, a.W = W, a.Co = Co, a.Ho = Ho, a.Wo = Wo, a.relu = relu;
+    a.nTx = (Wo + stem6::TW - 1) / stem6::TW;
+    a.nTy = (Ho + stem6::TH - 1) / stem6::TH;
+    a.ntiles = (int64_t)N * a.nTx * a.nTy;
+    a.edge_b = a.edge_r = nullptr;
+    a.Hp = a.Wp = 0;
+    return a;
+}
+unsigned stem_x6_grid(const StemX6Args &a) { return (unsigned)(a.ntiles < cu_count() ? a.ntiles : cu_count()); }
+
 }  // namespace
 
 namespace bev {
 int conv_x6_tune(int knob, int value) {
-    int *slot = knob == BEV_TUNE_CONV_X6_TILE ? &g_x6_tile : knob == BEV_TUNE_CONV_X6_NT ? &g_x6_nt : &g_x6_kernel;
-    if (value < 0 || value > (knob == BEV_TUNE_CONV_X6_TILE ? 2 : 1)) return BEV_ERR_ARGS;
-    const int old = *slot;
-    *slot = value;
-    return old;
+    if (knob == BEV_TUNE_CONV_X6_TILE) return swap_knob(g_x6_tile, value, 2);
+    return swap_knob(knob == BEV_TUNE_CONV_X6_NT ? g_x6_nt : g_x6_kernel, value, 1);
 }
 }  // namespace bev
 
@@ -1518,30 +1538,17 @@ int bev_conv_pack_weights_x6(const float *w, int Co, int Ci, int KH, int KW, uin
     const int64_t Kp = kpad_x(Ci * KH * KW), Cop = copad_x(Co), n = Kp * Cop;
     hipLaunchKernelGGL(k_pack_x6, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, Co, Ci, KH,
                        KW, Kp, Cop, (__bf16 *)packed);
-    return (int)hipGetLastError();
+    return last();
 }
 
 int bev_conv2d_x6_f32(const float *x, const uint16_t *xs, int N, int H, int W, int Ci, const uint16_t *packed,
                       const float *bias, const float *residual, int Co, int KH, int KW, int stride, int pad,
                       int dilation, int act, float *y, uint16_t *ys, int ldy, int Ho, int Wo, void *stream) {
-    if ((!x == !xs) || !packed || (!y == !ys) || N < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || KH <= 0 ||
-        KW <= 0 || stride <= 0 || pad < 0 || dilation <= 0 || act < 0 || act > 2 || ldy < Co)
-        return BEV_ERR_ARGS;
-    if (Ci % (xs ? YBK : XBK) != 0) return BEV_ERR_ARGS;  // one tap and 16 (split input: 32) channels per K step
-    if (Ho != (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 ||
-        Wo != (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1 || Ho <= 0 || Wo <= 0)
-        return BEV_ERR_ARGS;
-    if ((((uintptr_t)x | (uintptr_t)xs | (uintptr_t)packed) & 15) != 0) return BEV_ERR_ARGS;
-    if (residual && ldy != Co) return BEV_ERR_ARGS;
-    if (ys && (ldy != Co || Co % 4 != 0 || ((uintptr_t)ys & 7) != 0)) return BEV_ERR_ARGS;
-    if (N == 0) return 0;
-    ConvX a = conv_x6_args(x, packed, bias, residual, y, N, H, W, Ci, Co, KH, KW, stride, pad, dilation, Ho, Wo, act,
-                           ldy);
-    a.xs = (const __bf16 *)xs;
-    a.ys = (__bf16 *)ys;
-    a.xps = (int64_t)N * H * W * Ci;
-    a.yps = a.M * Co;
-    return dispatch_x6<false>(a, (hipStream_t)stream);
+    X6Call c{X6_PLAIN};
+    c.x = x, c.xs = xs, c.packed = packed, c.bias = bias, c.res = residual, c.y = y, c.ys = ys;
+    c.N = N, c.H = H, c.W = W, c.Ci = Ci, c.Co = Co, c.KH = KH, c.KW = KW, c.stride = stride, c.pad = pad;
+    c.dil = dilation, c.act = act, c.ldy = ldy, c.Ho = Ho, c.Wo = Wo;
+    return conv_x6(c, (hipStream_t)stream);
 }
 
 int bev_split3_f32(const float *x, int64_t n, uint16_t *planes, void *stream) {
@@ -1549,53 +1556,29 @@ int bev_split3_f32(const float *x, int64_t n, uint16_t *planes, void *stream) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_split3, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n,
                        (__bf16 *)planes);
-    return (int)hipGetLastError();
+    return last();
 }
 
 int bev_conv2d_dual_x6_f32(const float *x, int N, int Ho, int Wo, int Ci, const float *x2, int H2, int W2, int Ci2,
                            int stride2, const uint16_t *packed, const float *bias, int Co, int act, float *y,
                            void *stream) {
-    if (!x || !x2 || !packed || !y || N < 0 || Ho <= 0 || Wo <= 0 || Ci <= 0 || Ci2 <= 0 || H2 <= 0 || W2 <= 0 ||
-        stride2 <= 0 || Co <= 0 || act < 0 || act > 2)
-        return BEV_ERR_ARGS;
-    if (Ci % XBK != 0 || Ci2 % XBK != 0) return BEV_ERR_ARGS;
-    if (Ho != (H2 - 1) / stride2 + 1 || Wo != (W2 - 1) / stride2 + 1) return BEV_ERR_ARGS;
-    if ((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)packed) & 15) != 0) return BEV_ERR_ARGS;
-    if (N == 0) return 0;
-    ConvX a = conv_x6_args(x, packed, bias, nullptr, y, N, Ho, Wo, Ci, Co, 1, 1, 1, 0, 1, Ho, Wo, act, Co);
-    a.Kp = (int)kpad_x(Ci + Ci2);
-    a.x2 = x2;
-    a.Ci2 = Ci2, a.H2 = H2, a.W2 = W2, a.stride2 = stride2;
-    return dispatch_x6<true>(a, (hipStream_t)stream);
+    X6Call c{X6_DUAL};  // the 1x1 / stride 1 conv over x [N][Ho][Wo][Ci], K continued with x2's channels
+    c.x = x, c.packed = packed, c.bias = bias, c.y = y;
+    c.N = N, c.H = c.Ho = Ho, c.W = c.Wo = Wo, c.Ci = Ci, c.Co = c.ldy = Co, c.act = act;
+    c.x2 = x2, c.H2 = H2, c.W2 = W2, c.Ci2 = Ci2, c.stride2 = stride2;
+    return conv_x6(c, (hipStream_t)stream);
 }
 
 int bev_conv2d_chain_x6_f32(const float *x, const uint16_t *xs, int N, int H, int W, int Ci,
                             const uint16_t *packed, const float *bias, int Co, int KH, int KW, int stride, int pad,
                             int act, const uint16_t *packed2, const float *bias2, int Co2, const float *residual,
                             int act2, float *y, int Ho, int Wo, void *stream) {
-    if ((!x == !xs) || !packed || !packed2 || !y || N < 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 ||
-        stride <= 0 || pad < 0 || act < 0 || act > 2 || act2 < 0 || act2 > 2)
-        return BEV_ERR_ARGS;
-    if (Ci % YBK != 0 || (Co != 64 && Co != 128) || Co2 <= 0 || Co2 % 64 != 0 ||
-        (((uintptr_t)x | (uintptr_t)xs | (uintptr_t)packed | (uintptr_t)packed2) & 15) != 0)
-        return BEV_ERR_ARGS;
-    if (Ho != (H + 2 * pad - KH) / stride + 1 || Wo != (W + 2 * pad - KW) / stride + 1 || Ho <= 0 || Wo <= 0)
-        return BEV_ERR_ARGS;
-    if (N == 0) return 0;
-    ConvX a = conv_x6_args(x, packed, bias, residual, y, N, H, W, Ci, Co, KH, KW, stride, pad, 1, Ho, Wo, act, Co2);
-    a.xs = (const __bf16 *)xs;
-    a.xps = (int64_t)N * H * W * Ci;
-    a.wp2 = (const __bf16 *)packed2;
-    a.bias2 = bias2;
-    a.Co2 = Co2, a.act2 = act2;
-    if (Co != 64 && Co2 % 128 != 0) return BEV_ERR_ARGS;  // two waves share each 32-row band of the 64-row tile
-    const hipStream_t st = (hipStream_t)stream;
-    if (xs) {  // conv1 handed over its output split: conv2's operand by LDS-DMA (k_conv_x6s), same K order
-        if (Co == 64) return launch_x6<128, 64>(k_conv_x6s<4, 1, 1, 2, 1>, a, st);
-        return launch_x6<64, 128>(k_conv_x6s<2, 2, 1, 2, 1>, a, st);
-    }
-    if (Co == 64) return launch_x6<128, 64>(k_conv_x6b<4, 1, 1, 2, false, 1>, a, st);
-    return launch_x6<64, 128>(k_conv_x6b<2, 2, 1, 2, false, 1>, a, st);  // 64 x 128: h2 planes 52 KiB of LDS
+    X6Call c{X6_CHAIN};
+    c.x = x, c.xs = xs, c.packed = packed, c.bias = bias, c.res = residual, c.y = y;
+    c.N = N, c.H = H, c.W = W, c.Ci = Ci, c.Co = Co, c.KH = KH, c.KW = KW, c.stride = stride, c.pad = pad;
+    c.act = act, c.Ho = Ho, c.Wo = Wo;
+    c.packed2 = packed2, c.bias2 = bias2, c.Co2 = Co2, c.act2 = act2;
+    return conv_x6(c, (hipStream_t)stream);
 }
 
 int bev_conv2d_chain_dual_x6_f32(const float *x, const uint16_t *xs, int N, int H, int W, int Ci,
@@ -1603,100 +1586,50 @@ int bev_conv2d_chain_dual_x6_f32(const float *x, const uint16_t *xs, int N, int 
                                  int pad, int act, const float *x2, int H2, int W2, int Ci2, int stride2,
                                  const uint16_t *packed2, const float *bias2, int Co2, int act2, float *y, int Ho,
                                  int Wo, void *stream) {
-    if ((!x == !xs) || !x2 || !packed || !packed2 || !y || N < 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 ||
-        stride <= 0 || pad < 0 || act < 0 || act > 2 || act2 < 0 || act2 > 2 || stride2 <= 0 || H2 <= 0 || W2 <= 0)
-        return BEV_ERR_ARGS;
-    // the layer1 block-0 shape: 64-channel h2 and a 64-channel shortcut operand (4 slices kept in registers)
-    if (Ci % YBK != 0 || Co != 64 || Ci2 != 64 || Co2 <= 0 || Co2 % 64 != 0 ||
-        (((uintptr_t)x | (uintptr_t)xs | (uintptr_t)x2 | (uintptr_t)packed | (uintptr_t)packed2) & 15) != 0)
-        return BEV_ERR_ARGS;
-    if (Ho != (H + 2 * pad - KH) / stride + 1 || Wo != (W + 2 * pad - KW) / stride + 1 || Ho <= 0 || Wo <= 0 ||
-        Ho != (H2 - 1) / stride2 + 1 || Wo != (W2 - 1) / stride2 + 1)
-        return BEV_ERR_ARGS;
-    if (N == 0) return 0;
-    ConvX a = conv_x6_args(x, packed, bias, nullptr, y, N, H, W, Ci, Co, KH, KW, stride, pad, 1, Ho, Wo, act, Co2);
-    a.x2 = x2;
-    a.Ci2 = Ci2, a.H2 = H2, a.W2 = W2, a.stride2 = stride2;
-    a.xs = (const __bf16 *)xs;
-    a.xps = (int64_t)N * H * W * Ci;
-    a.wp2 = (const __bf16 *)packed2;
-    a.bias2 = bias2;
-    a.Co2 = Co2, a.act2 = act2;
-    if (xs) return launch_x6<128, 64>(k_conv_x6s<4, 1, 1, 2, 2>, a, (hipStream_t)stream);
-    return launch_x6<128, 64>(k_conv_x6b<4, 1, 1, 2, false, 2>, a, (hipStream_t)stream);
+    X6Call c{X6_CHAIN_DUAL};
+    c.x = x, c.xs = xs, c.packed = packed, c.bias = bias, c.y = y;
+    c.N = N, c.H = H, c.W = W, c.Ci = Ci, c.Co = Co, c.KH = KH, c.KW = KW, c.stride = stride, c.pad = pad;
+    c.act = act, c.Ho = Ho, c.Wo = Wo;
+    c.x2 = x2, c.H2 = H2, c.W2 = W2, c.Ci2 = Ci2, c.stride2 = stride2;
+    c.packed2 = packed2, c.bias2 = bias2, c.Co2 = Co2, c.act2 = act2;
+    return conv_x6(c, (hipStream_t)stream);
 }
 
 int bev_conv2d_stem_x6_f32(const float *x, int N, int H, int W, const uint16_t *packed, const float *bias, int Co,
                            int relu, float *y, int Ho, int Wo, void *stream) {
     if (!x || !packed || !bias || !y || N <= 0 || H <= 0 || W <= 0 || Co <= 0 || Co > 64 ||
-        Ho != (H + 6 - 7) / 2 + 1 || Wo != (W + 6 - 7) / 2 + 1 || (((uintptr_t)packed) & 15) != 0)
+        Ho != conv_out(H, 3, 1, 7, 2) || Wo != conv_out(W, 3, 1, 7, 2) || (((uintptr_t)packed) & 15) != 0)
         return BEV_ERR_ARGS;
-    static int num_cu = 0;
-    if (num_cu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        num_cu = n;
-    }
-    StemX6Args a;
-    a.x = x;
-    a.wp = (const __bf16 *)packed;
-    a.bias = bias;
-    a.y = y;
-    a.H = H, a.W = W, a.Co = Co, a.Ho = Ho, a.Wo = Wo, a.relu = relu;
-    a.nTx = (Wo + stem6::TW - 1) / stem6::TW;
-    a.nTy = (Ho + stem6::TH - 1) / stem6::TH;
-    a.ntiles = (int64_t)N * a.nTx * a.nTy;
-    a.edge_b = a.edge_r = nullptr;
-    a.Hp = a.Wp = 0;
-    const int64_t grid = a.ntiles < num_cu ? a.ntiles : num_cu;
-    hipLaunchKernelGGL(k_stem_x6<false>, dim3((unsigned)grid), dim3(stem6::NTHR), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    const StemX6Args a = stem_x6_args(x, N, H, W, packed, bias, Co, relu, y, Ho, Wo);
+    hipLaunchKernelGGL(k_stem_x6<false>, dim3(stem_x6_grid(a)), dim3(stem6::NTHR), 0, (hipStream_t)stream, a);
+    return last();
 }
 
 int64_t bev_conv2d_stem_pool_x6_workspace(int N, int H, int W) {
     if (N <= 0 || H <= 0 || W <= 0) return BEV_ERR_ARGS;
-    const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    const int64_t nt = (int64_t)N * ((Wo + stem6::TW - 1) / stem6::TW) * ((Ho + stem6::TH - 1) / stem6::TH);
-    return nt * (32 + 5) * 64 * (int64_t)sizeof(float);
+    const StemX6Args a = stem_x6_args(nullptr, N, H, W, nullptr, nullptr, 64, 1, nullptr, conv_out(H, 3, 1, 7, 2),
+                                      conv_out(W, 3, 1, 7, 2));
+    return a.ntiles * (32 + 5) * 64 * (int64_t)sizeof(float);
 }
 
 int bev_conv2d_stem_pool_x6_f32(const float *x, int N, int H, int W, const uint16_t *packed, const float *bias,
                                 int Co, float *y, int Hp, int Wp, void *workspace, int64_t workspace_bytes,
                                 void *stream) {
-    const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
+    const int Ho = conv_out(H, 3, 1, 7, 2), Wo = conv_out(W, 3, 1, 7, 2);
     if (!x || !packed || !bias || !y || !workspace || N <= 0 || H <= 0 || W <= 0 || Co != 64 ||
-        Hp != (Ho + 2 - 3) / 2 + 1 || Wp != (Wo + 2 - 3) / 2 + 1 || (((uintptr_t)packed | (uintptr_t)y |
-                                                                       (uintptr_t)workspace) & 15) != 0)
+        Hp != conv_out(Ho, 1, 1, 3, 2) || Wp != conv_out(Wo, 1, 1, 3, 2) ||
+        (((uintptr_t)packed | (uintptr_t)y | (uintptr_t)workspace) & 15) != 0)
         return BEV_ERR_ARGS;
     if (workspace_bytes < bev_conv2d_stem_pool_x6_workspace(N, H, W)) return BEV_ERR_ARGS;
-    static int num_cu = 0;
-    if (num_cu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        num_cu = n;
-    }
-    StemX6Args a;
-    a.x = x;
-    a.wp = (const __bf16 *)packed;
-    a.bias = bias;
-    a.y = y;
-    a.H = H, a.W = W, a.Co = Co, a.Ho = Ho, a.Wo = Wo, a.relu = 1;
-    a.nTx = (Wo + stem6::TW - 1) / stem6::TW;
-    a.nTy = (Ho + stem6::TH - 1) / stem6::TH;
-    a.ntiles = (int64_t)N * a.nTx * a.nTy;
+    StemX6Args a = stem_x6_args(x, N, H, W, packed, bias, Co, 1, y, Ho, Wo);
     a.edge_b = (float *)workspace;
     a.edge_r = a.edge_b + a.ntiles * 32 * 64;
     a.Hp = Hp, a.Wp = Wp;
-    const int64_t grid = a.ntiles < num_cu ? a.ntiles : num_cu;
-    hipLaunchKernelGGL(k_stem_x6<true>, dim3((unsigned)grid), dim3(stem6::NTHR), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_stem_x6<true>, dim3(stem_x6_grid(a)), dim3(stem6::NTHR), 0, (hipStream_t)stream, a);
     const int64_t nthr = a.ntiles * 35 * 16;
     hipLaunchKernelGGL(k_stem_pool_seams, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y,
                        a.edge_b, a.edge_r, a.nTx, a.nTy, a.ntiles, Hp, Wp);
-    return (int)hipGetLastError();
+    return last();
 }
 
 }  // extern "C"

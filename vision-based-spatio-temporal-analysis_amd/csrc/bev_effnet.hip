@@ -26,6 +26,8 @@
 
 #include "../../include/bev_mi355x.h"
 #include "bev_act.h"
+#include "bev_mfma.h"
+#include "bev_tune.h"
 
 namespace {
 
@@ -632,11 +634,6 @@ __global__ __launch_bounds__(64 * IR_W) void k_irdw(const float *__restrict__ x,
     if (p == 0) *(irf4 *)(psum + ((int64_t)n * strips * segs + blk) * Cm + ch0 + 4 * q) = ssum;
 }
 
-inline int last() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 // Which depthwise kernel: the row runs for stride 1 / 2 wherever the channel quads split into equal chunks of at most
 // 64, else the per-pixel k_dwconv.  The choice depends on (C, stride) and BEV_TUNE_DW_RUN only, and the SE partial
 // count (bev_dwconv_psum_blocks) and the launch both take it from here.
@@ -650,10 +647,7 @@ inline int dw_run_blocks(int Ho, int Wo, int C, int stride) {
 
 namespace bev {
 int stem3_tune(int value) {
-    if (value < 0 || value > 2) return BEV_ERR_ARGS;
-    const int old = g_stem3_stage;
-    g_stem3_stage = value;
-    return old;
+    return swap_knob(g_stem3_stage, value, 2);
 }
 int dw_tune(int value) {
     if (value != 0 && value != 3) return BEV_ERR_ARGS;  // 1 / 2: retired arms

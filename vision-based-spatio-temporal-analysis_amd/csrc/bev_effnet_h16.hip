@@ -18,6 +18,7 @@
 
 #include "../../include/bev_mi355x.h"
 #include "bev_act.h"
+#include "bev_mfma.h"
 
 namespace {
 
@@ -30,11 +31,6 @@ __device__ __forceinline__ float act_f(float t, int act) {
     if (act == 1) return relu_f(t);
     if (act == 2) return silu_hw(t);
     return t;
-}
-
-inline int last() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
 }
 
 // ---- depthwise ---------------------------------------------------------------------------------------------------

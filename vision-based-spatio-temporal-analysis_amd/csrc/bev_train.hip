@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/bev_mi355x.h"
+#include "bev_mfma.h"
 #include "bev_tune.h"
 
 namespace {
@@ -27,11 +28,6 @@ namespace {
 int g_wgrad_mfma = 2;  // bev_tune(BEV_TUNE_WGRAD_MFMA): 2 = k_wgrad_nat (default), 1 = k_wgrad_mfma, 0 = k_wgrad_v4
 typedef float wf32x16 __attribute__((ext_vector_type(16)));
 typedef float wf32x4 __attribute__((ext_vector_type(4)));
-
-inline int last() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
 
 __global__ __launch_bounds__(256) void k_relu_bwd(const float *__restrict__ dy, const float *__restrict__ y,
                                                   float *__restrict__ dz, int64_t n4) {
@@ -232,21 +228,6 @@ __global__ __launch_bounds__(256) void k_wgrad_v4(const float *__restrict__ x, c
 // consecutive dwords.  Same tiles, m split and float-atomic epilogue as k_wgrad_mfma below.
 __device__ __attribute__((aligned(16))) float g_wzero4[4] = {0.f, 0.f, 0.f, 0.f};  // never written
 
-__device__ __forceinline__ unsigned wg_lds_base(const void *p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char *)p;
-}
-
-__device__ __forceinline__ void wg_dma16(const float *src, unsigned dst_any) {
-    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)dst_any);  // wave-uniform LDS address
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(dst)
-        : "memory");
-}
-
 template <int WCO, int TM, int TN>
 __global__ __launch_bounds__(256, TN == 4 ? 1 : 2) void k_wgrad_nat(const float *__restrict__ x, const float *__restrict__ dz, int N,
                                                       int H, int W, int Ci, int Ho, int Wo, int Co, int KW, int K,
@@ -258,11 +239,7 @@ __global__ __launch_bounds__(256, TN == 4 ? 1 : 2) void k_wgrad_nat(const float 
     constexpr int STAGE = 32 * (CT + KT);               // floats per stage
     static_assert((32 * AF) % 256 == 0 && (32 * BF) % 256 == 0, "whole DMA instructions per wave");
     __shared__ __attribute__((aligned(16))) float lds[2 * STAGE];
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);
     const int tile = (int)(bid % (unsigned)ntiles);
     const int64_t split = bid / (unsigned)ntiles;
     const int co0 = (tile % ctiles) * CT, k0 = (tile / ctiles) * KT;
@@ -280,7 +257,7 @@ __global__ __launch_bounds__(256, TN == 4 ? 1 : 2) void k_wgrad_nat(const float 
         mpy = (int)(t % Ho);
         mpn = (int)(t / Ho);
     }
-    const unsigned lbase = wg_lds_base(lds);
+    const unsigned lbase = lds_addr(lds);
     int64_t ms = mb;
     auto issue = [&](int buf) {
         const unsigned d0 = lbase + (unsigned)(buf * STAGE * 4);
@@ -289,7 +266,7 @@ __global__ __launch_bounds__(256, TN == 4 ? 1 : 2) void k_wgrad_nat(const float 
             const int f = (wave + 4 * q) * 64 + lane, row = f / AF, col = f % AF;
             const int64_t m = ms + row;
             const float *src = (m < me && co0 + 4 * col < Co) ? dz + m * Co + co0 + 4 * col : g_wzero4;
-            wg_dma16(src, d0 + (unsigned)((wave + 4 * q) * 1024));
+            lds_dma16(src, d0 + (unsigned)((wave + 4 * q) * 1024));
         }
 #pragma unroll
         for (int q = 0; q < QB; ++q) {
@@ -307,7 +284,7 @@ __global__ __launch_bounds__(256, TN == 4 ? 1 : 2) void k_wgrad_nat(const float 
             const int iy = py * stride - pad + ky * dil, ix = px * stride - pad + kx * dil;
             const bool in = ms + row < me && k < K && iy >= 0 && iy < H && ix >= 0 && ix < W;
             const float *src = in ? x + (((int64_t)pn * H + iy) * W + ix) * Ci + ci : g_wzero4;
-            wg_dma16(src, d0 + (unsigned)(CT * 32 * 4 + (wave + 4 * q) * 1024));
+            lds_dma16(src, d0 + (unsigned)(CT * 32 * 4 + (wave + 4 * q) * 1024));
         }
         ms += 32;
         mpx += 32;
@@ -418,11 +395,7 @@ __global__ __launch_bounds__(256, TN == 4 ? 1 : 2) void k_wgrad_mfma(const float
     constexpr int BCOLS = KT / 4, BRPP = 256 / BCOLS, BQ = WM_BM / BRPP;
     constexpr int STAGE = (CT + KT) * WM_LROW;
     __shared__ __attribute__((aligned(16))) float lds[NBUF * STAGE];
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, xc = bid % 8;
-        bid = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + bid / 8;
-    }
+    const unsigned bid = xcd_block(blockIdx.x, gridDim.x);
     const int tile = (int)(bid % (unsigned)ntiles);
     const int64_t split = bid / (unsigned)ntiles;
     const int co0 = (tile % ctiles) * CT, k0 = (tile / ctiles) * KT;
@@ -1085,9 +1058,6 @@ int bev_maxpool2d_bwd_ws_nhwc_f32(const float *x, const float *dy, int N, int H,
 
 namespace bev {
 int train_tune(int knob, int value) {
-    if (knob != BEV_TUNE_WGRAD_MFMA || value < 0 || value > 2) return BEV_ERR_ARGS;
-    const int old = g_wgrad_mfma;
-    g_wgrad_mfma = value;
-    return old;
+    return knob == BEV_TUNE_WGRAD_MFMA ? swap_knob(g_wgrad_mfma, value, 2) : BEV_ERR_ARGS;
 }
 }  // namespace bev

@@ -1,8 +1,16 @@
-// bev_tune.h -- internal: performance knobs of the warp (bev_warp.hip) and training (bev_train.hip) kernels, set through
-// bev_tune() (bev_conv.hip).  Results never depend on them.
+// bev_tune.h -- internal: the per-source halves of bev_tune() (bev_conv.hip), which sets the performance knobs.
+// Results never depend on them.
 #pragma once
 
 namespace bev {
+
+// What setting a knob does: a value outside 0..max is refused (-1 = BEV_ERR_ARGS), else the previous value is returned.
+inline int swap_knob(int &slot, int value, int max) {
+    if (value < 0 || value > max) return -1;
+    const int old = slot;
+    slot = value;
+    return old;
+}
 
 // knob = BEV_TUNE_WARP_* (include/bev_mi355x.h); returns the previous value or BEV_ERR_ARGS.
 int warp_tune(int knob, int value);
