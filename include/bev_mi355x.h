@@ -869,6 +869,46 @@ int bev_image_resize_plan(int Hs, int Ws, int H, int W, void *host_buf, int64_t 
  * is a no-op.  (Hs, Ws) == (H, W) runs bev_image_normalize_u8_f32's kernels.  Element offsets are 64-bit. */
 int bev_image_resize_normalize_u8_f32(const uint8_t *src, int N, int Hs, int Ws, const void *plan_dev, int H, int W,
                                       const float *mean, const float *std, float *out, void *stream);
+/* device: the same resize with the resized frame itself stored, out_u8 [N][H][W][3] uint8 (any alignment; dword
+ * stores when W % 4 == 0 and out_u8 is 4-B aligned), bit-identical to img.resize((W, H), Image.BILINEAR): the same
+ * kernel with a second epilogue, the same geometry rules and argument checks.  (Hs, Ws) == (H, W) is a device copy
+ * on the stream.  Added under ABI 17's additions, as the entries below. */
+int bev_image_resize_u8(const uint8_t *src, int N, int Hs, int Ws, const void *plan_dev, int H, int W, uint8_t *out_u8,
+                        void *stream);
+
+/* Colour jitter on the device: T.RandomApply([T.ColorJitter(0.2, 0.2, 0.2, 0.05)], p=0.5) (data/transforms.py:14,
+ * applied per image between T.Resize and T.ToTensor, wildtrack_loader.py:368-374), torchvision's PIL path:
+ * PIL.ImageEnhance Brightness / Contrast / Color (ImagingBlend of a degenerate image and the frame, in C float) and
+ * the hue shift through Pillow's RGB <-> HSV conversions, in the drawn order, each result uint8 before the next op.
+ * The random draws stay on the host; each frame carries one record of eight 32-bit words, params [N][8]:
+ *   word 0     the op list in application order, four bits per op: 1 brightness, 2 contrast, 3 saturation, 4 hue,
+ *              0 ends the list (word 0 == 0: the frame is not jittered); any other code is a no-op
+ *   words 1-3  the brightness, contrast and saturation factors, fp32 bits (the Python double converted to float)
+ *   word 4     the hue shift byte (torchvision's uint8(hue_factor * 255)); only its low 8 bits are read
+ *   words 5-7  zero, reserved
+ * Results are Pillow's bit for bit for finite factors >= 0 (csrc/bev_image_jitter.h holds the per-pixel functions,
+ * shared by the kernels and the host entry); for other factors they are unspecified, and no bit pattern makes a kernel
+ * leave its buffers.  Contrast blends with the rounded mean of L over the frame as the ops before it in the list leave
+ * it: the one cross-pixel dependency, an exact integer sum per frame in the workspace (a list naming contrast more
+ * than once, which ColorJitter never draws, uses the first one's mean for each).
+ *
+ * host: bytes of the workspace for N frames (8 per frame). */
+int64_t bev_image_jitter_workspace_bytes(int N);
+/* device: src [N][H][W][3] uint8 RGB at the output size, any byte alignment -> out [N][3][H][W] fp32 (4-B aligned):
+ * each frame's op list, then T.ToTensor + T.Normalize as bev_image_normalize_u8_f32 (a frame with an empty list gets
+ * exactly its result).  params: device, 4-B aligned; mean, std: host float[3]; workspace: device, 8-B aligned,
+ * workspace_bytes >= bev_image_jitter_workspace_bytes(N), zeroed here on the stream.  Two passes (the L sums of the
+ * frames with contrast, then the whole list); float4 non-temporal stores when H * W % 4 == 0, src is 4-B and out 16-B
+ * aligned.  Allocates nothing and synchronises nothing.  Arguments are checked on the host before any launch:
+ * BEV_ERR_ARGS for a null or misaligned pointer, N < 0, a non-positive size or a workspace that is too small; N == 0
+ * is a no-op. */
+int bev_image_jitter_normalize_u8_f32(const uint8_t *src, int N, int H, int W, const int32_t *params, const float *mean,
+                                      const float *std, void *workspace, int64_t workspace_bytes, float *out,
+                                      void *stream);
+/* host, no HIP call: the same per-pixel functions on the CPU, src and out_u8 [N][H][W][3] uint8 in host memory (out_u8
+ * may be src), params [N][8] in host memory.  The jittered uint8 frames: what ColorJitter hands to ToTensor.  For
+ * checking the arithmetic without a GPU, and for another host to check its own port against. */
+int bev_image_jitter_u8_host(const uint8_t *src, int N, int H, int W, const int32_t *params, uint8_t *out_u8);
 
 /* BEVNet head operand (model_wrapper.py:69-75 -- proj bias add, pos-enc concat; the reference's torch.cat of the
  * projection [B,P,Hb,Wb] and pos_enc [2,Hb,Wb]): x [B][Hb][Wb][cp] channels-last = (s + bias, pos, 0...) per cell, s the

@@ -135,6 +135,10 @@ SIGNATURES = {
     "bev_image_resize_plan_bytes": (_i64, [_i, _i, _i, _i]),
     "bev_image_resize_plan": (_i, [_i, _i, _i, _i, _vp, _i64]),
     "bev_image_resize_normalize_u8_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "bev_image_resize_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "bev_image_jitter_workspace_bytes": (_i64, [_i]),
+    "bev_image_jitter_normalize_u8_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "bev_image_jitter_u8_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "bev_groupnorm_bwd_f32": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "bev_conv_packed_size_h16": (_i64, [_i, _i, _i, _i]),
     "bev_conv_pack_weights_h16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
@@ -2125,4 +2129,104 @@ def image_resize_normalize_u8(src: torch.Tensor, out_hw, mean, std, out: torch.T
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
     _check(lib().bev_image_resize_normalize_u8_f32(_ptr(src), N, Hs, Ws, _ptr(plan), H, W, m, s, _ptr(out),
                                                    _stream(src)), "bev_image_resize_normalize_u8_f32")
+    return out
+
+
+def image_resize_u8(src: torch.Tensor, out_hw, out: torch.Tensor = None) -> torch.Tensor:
+    """[N, Hs, Ws, 3] uint8 RGB on the GPU -> [N, H, W, 3] uint8: PIL's BILINEAR Resize((H, W)) alone
+    (bev_image_resize_u8, the resize kernel's uint8 epilogue), bit-identical to `img.resize((W, H), Image.BILINEAR)`.
+    Shares the per-geometry coefficient tables of image_resize_normalize_u8."""
+    if not src.is_cuda:
+        raise HipError("image_resize_u8 needs a ROCm device tensor (got a CPU tensor); no CPU fallback")
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"image_resize_u8 expects [N, Hs, Ws, 3] uint8, got {tuple(src.shape)} {src.dtype}")
+    H, W = (int(v) for v in out_hw)
+    src = src.contiguous()
+    N, Hs, Ws, _ = src.shape
+    if out is None:
+        out = torch.empty(N, H, W, 3, device=src.device, dtype=torch.uint8)
+    elif (not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous()):
+        raise ValueError(f"image_resize_u8: out must be a contiguous [{N}, {H}, {W}, 3] uint8 device tensor")
+    plan = _resize_plan_dev(src.device, Hs, Ws, H, W)
+    _check(lib().bev_image_resize_u8(_ptr(src), N, Hs, Ws, _ptr(plan), H, W, _ptr(out), _stream(src)),
+           "bev_image_resize_u8")
+    return out
+
+
+JITTER_OPS = {"brightness": 1, "contrast": 2, "saturation": 3, "hue": 4}  # include/bev_mi355x.h: op codes of word 0
+
+
+def _check_jitter_params(params, n: int, who: str):
+    """A host copy of the records ([n, 8] int32 numpy) after the checks the device cannot make: finite factors >= 0
+    (the range the results are specified for) and contrast at most once per list."""
+    import numpy as np
+    rec = np.ascontiguousarray(params)
+    if rec.dtype != np.int32 or rec.shape != (n, 8):
+        raise ValueError(f"{who}: params must be int32 [{n}, 8], got {rec.dtype} {tuple(rec.shape)}")
+    factors = rec[:, 1:4].view(np.float32)
+    if not (np.isfinite(factors) & (factors >= 0)).all():
+        raise ValueError(f"{who}: brightness / contrast / saturation factors must be finite and >= 0")
+    ops = rec[:, 0].astype(np.int64) & 0xFFFFFFFF
+    contrasts, live = np.zeros(n, dtype=np.int64), np.ones(n, dtype=bool)
+    for i in range(8):
+        code = (ops >> (4 * i)) & 15
+        live &= code != 0
+        contrasts += live & (code == JITTER_OPS["contrast"])
+    if (contrasts > 1).any():
+        raise ValueError(f"{who}: an op list names contrast more than once")
+    return rec
+
+
+def image_jitter_normalize_u8(src: torch.Tensor, params: torch.Tensor, mean, std,
+                              out: torch.Tensor = None) -> torch.Tensor:
+    """[N, H, W, 3] uint8 RGB on the GPU + one jitter record per frame (int32 [N, 8]: include/bev_mi355x.h,
+    `data.transforms.ColorJitter.params_record`) -> [N, 3, H, W] fp32: ColorJitter in each frame's drawn order, then
+    ToTensor + Normalize (bev_image_jitter_normalize_u8_f32), bit-identical to the CPU transforms on PIL.  `params` on
+    the CPU is validated (ValueError for a NaN or negative factor) and copied to the device; on the device it is
+    used as it is."""
+    if not src.is_cuda:
+        raise HipError("image_jitter_normalize_u8 needs a ROCm device tensor (got a CPU tensor); no CPU fallback")
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"image_jitter_normalize_u8 expects [N, H, W, 3] uint8, got {tuple(src.shape)} {src.dtype}")
+    src = src.contiguous()
+    N, H, W, _ = src.shape
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.int32 or tuple(params.shape) != (N, 8):
+        raise ValueError(f"image_jitter_normalize_u8: params must be an int32 [{N}, 8] tensor")
+    if params.is_cuda:
+        if params.device != src.device:
+            raise ValueError("image_jitter_normalize_u8: params is on another device than src")
+        params = params.contiguous()
+    else:
+        _check_jitter_params(params.numpy(), N, "image_jitter_normalize_u8")
+        params = params.contiguous().to(src.device)
+    if out is None:
+        out = torch.empty(N, 3, H, W, device=src.device, dtype=torch.float32)
+    elif (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, 3, H, W)
+          or not out.is_contiguous()):
+        raise ValueError(f"image_jitter_normalize_u8: out must be a contiguous [{N}, 3, {H}, {W}] fp32 device tensor")
+    L = lib()
+    nbytes = int(L.bev_image_jitter_workspace_bytes(N))
+    work = torch.empty(max(nbytes // 8, 1), device=src.device, dtype=torch.int64)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    _check(L.bev_image_jitter_normalize_u8_f32(_ptr(src), N, H, W, _ptr(params), m, s, _ptr(work), nbytes, _ptr(out),
+                                               _stream(src)), "bev_image_jitter_normalize_u8_f32")
+    return out
+
+
+def image_jitter_u8_host(src, params):
+    """The jitter alone on the CPU (bev_image_jitter_u8_host: the kernels' per-pixel functions compiled for the host;
+    no GPU needed): src [N, H, W, 3] uint8 numpy, params [N, 8] int32 numpy -> the jittered uint8 frames, what
+    ColorJitter hands to ToTensor.  The way to check the arithmetic, or another host's port of it, against Pillow."""
+    import numpy as np
+    src = np.ascontiguousarray(src)
+    if src.dtype != np.uint8 or src.ndim != 4 or src.shape[3] != 3:
+        raise ValueError(f"image_jitter_u8_host expects [N, H, W, 3] uint8, got {src.shape} {src.dtype}")
+    N, H, W, _ = src.shape
+    rec = _check_jitter_params(params, N, "image_jitter_u8_host")
+    out = np.empty_like(src)
+    if N:
+        _check(lib().bev_image_jitter_u8_host(ctypes.c_void_p(src.ctypes.data), N, H, W,
+                                              ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(out.ctypes.data)),
+               "bev_image_jitter_u8_host")
     return out

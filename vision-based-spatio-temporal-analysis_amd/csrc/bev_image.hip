@@ -36,11 +36,20 @@
 // 4 consecutive output pixels (one ds_read_b128 per tap), then norm1 and one float4 per plane,
 // non-temporal, when W % 4 == 0 and out is 16-B aligned (scalar stores otherwise).  HBM traffic per
 // image: 3 * Hs * Ws bytes read (+ the tiles' row overlap, which L2 serves) and 12 * H * W written.
+//
+// bev_image_resize_u8 + bev_image_jitter_normalize_u8_f32 put the step between the two on the device as well:
+// T.RandomApply([T.ColorJitter(0.2, 0.2, 0.2, 0.05)], p=0.5) (transforms.py:14).  The resize kernel's second epilogue
+// stores the resized uint8 frame; the jitter kernels apply each frame's drawn op list (a record of eight words, drawn
+// on the host in the reference's order) with the per-pixel functions of bev_image_jitter.h -- Pillow's ImagingBlend
+// and RGB <-> HSV conversions, type for type -- then norm1.  Contrast needs the mean of L over the frame as its
+// predecessors leave it: pass 1 sums L per frame (exact integers, one 64-bit atomic per workgroup), pass 2 applies the
+// whole list.  Per output pixel that adds 3 B written and 3 + 3 B read to the 12 B written (DESIGN.md §4 has the times).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/bev_mi355x.h"
+#include "bev_image_jitter.h"
 
 namespace {
 
@@ -193,12 +202,14 @@ __device__ __forceinline__ void rs_hpass(const uint32_t *__restrict__ base, int6
 
 // dynamic LDS: inter [rcap][64] dwords | x coeffs [64][ksx] | y coeffs [TH][ksy] | x bounds [64][2] | y bounds [TH][2]
 // NG = 1, 2, 3: every horizontal window has at most 4 NG taps (ksize_x <= 4 NG + 1); NG = 0: any window
-template <int NG>
+// U8: the epilogue stores the resized frame itself, [N][H][W][3] uint8 (out_v: uint8; vec: W % 4 == 0 and out 4-B aligned,
+// a lane's 4 pixels = 3 dwords), for the jitter that follows; otherwise norm1 and the fp32 planes (out_v: float)
+template <int NG, bool U8>
 __global__ __launch_bounds__(256) void k_img_resize_norm(const uint8_t *__restrict__ src, int Hs, int Ws, int H, int W,
                                                          const int32_t *__restrict__ xb, const int32_t *__restrict__ xk,
                                                          const int32_t *__restrict__ yb, const int32_t *__restrict__ yk,
                                                          int ksx, int ksy, int TH, int rcap, int tiles_x, int tiles_y,
-                                                         int64_t last_dw, Norm nm, float *__restrict__ out, int vec) {
+                                                         int64_t last_dw, Norm nm, void *__restrict__ out_v, int vec) {
     extern __shared__ __attribute__((aligned(16))) uint32_t rs_lds[];
     uint32_t *inter = rs_lds;
     int32_t *sxk = (int32_t *)(inter + rcap * RS_TW);
@@ -272,7 +283,7 @@ __global__ __launch_bounds__(256) void k_img_resize_norm(const uint8_t *__restri
 
     // vertical pass out of LDS, normalise, store the three planes
     const int64_t plane = (int64_t)H * W;
-    float *o = out + (int64_t)n * 3 * plane;
+    float *o = (float *)out_v + (int64_t)n * 3 * plane;
     for (int q = tid; q < th * (RS_TW / 4); q += 256) {
         const int ty = q / (RS_TW / 4), qx = q % (RS_TW / 4);
         if (4 * qx >= tw) continue;
@@ -294,7 +305,25 @@ __global__ __launch_bounds__(256) void k_img_resize_norm(const uint8_t *__restri
                 for (int c = 0; c < 3; ++c) acc[p][c] += (int)((w4[p] >> (8 * c)) & 255u) * kk;
         }
         const int64_t at = (int64_t)(y0 + ty) * W + x0 + 4 * qx;
-        if (vec) {
+        if constexpr (U8) {
+            uint8_t *o8 = (uint8_t *)out_v + ((int64_t)n * plane + at) * 3;
+            if (vec) {
+                uint32_t w[3] = {0, 0, 0};
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) w[(3 * p + c) / 4] |= rs_clip8(acc[p][c]) << (8 * ((3 * p + c) % 4));
+#pragma unroll
+                for (int j = 0; j < 3; ++j) ((uint32_t *)o8)[j] = w[j];
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    if (4 * qx + p >= tw) break;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) o8[3 * p + c] = (uint8_t)rs_clip8(acc[p][c]);
+                }
+            }
+        } else if (vec) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float m = nm.mean[c], s = nm.std[c];
@@ -311,6 +340,134 @@ __global__ __launch_bounds__(256) void k_img_resize_norm(const uint8_t *__restri
             }
         }
     }
+}
+
+// ---- ColorJitter + ToTensor + Normalize ------------------------------------------------------------------
+// A workgroup of 256 lanes takes JIT_PX(VEC) consecutive pixels of ONE frame (grid = blocks per frame x N), so the
+// frame's record is wave-uniform: s_loads, and the op-order branches of bev_jitter::apply do not diverge.  VEC: a lane
+// = 4 consecutive pixels, as k_img_norm_v4 (H*W % 4 == 0, src 4-B aligned, out 16-B aligned); otherwise one pixel.
+namespace jit = bev_jitter;
+
+template <bool VEC>
+constexpr int JIT_PX = VEC ? 1024 : 256;
+
+// a lane's pixels of frame n: index i0 .. i0 + NP - 1 < hw (false: none)
+template <bool VEC>
+__device__ __forceinline__ bool jit_load(const uint8_t *__restrict__ src, int64_t n, int blk, int64_t hw,
+                                         unsigned (&c)[VEC ? 4 : 1][3], int64_t &i0) {
+    i0 = (int64_t)blk * JIT_PX<VEC> + (int64_t)threadIdx.x * (VEC ? 4 : 1);
+    if (i0 >= hw) return false;
+    if constexpr (VEC) {
+        const uint32_t *s = (const uint32_t *)src + (n * hw + i0) / 4 * 3;
+        const uint32_t w0 = s[0], w1 = s[1], w2 = s[2];
+        const unsigned b[12] = {w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u, w0 >> 24,
+                                w1 & 255u, (w1 >> 8) & 255u, (w1 >> 16) & 255u, w1 >> 24,
+                                w2 & 255u, (w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24};
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[p][k] = b[3 * p + k];
+    } else {
+        const uint8_t *s = src + (n * hw + i0) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[0][k] = s[k];
+    }
+    return true;
+}
+
+// Pass 1: sum of L over each frame whose list holds contrast, of the frame as its predecessors in the list leave it.
+// Integer sums: one 64-bit atomic add per workgroup gives the same total in any order.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_img_jitter_sum(const uint8_t *__restrict__ src, int64_t hw, int bpf,
+                                                        const uint32_t *__restrict__ params,
+                                                        unsigned long long *__restrict__ sums) {
+    __shared__ unsigned wave_sum[4];
+    const int n = blockIdx.x / bpf, blk = blockIdx.x - n * bpf;
+    const jit::Rec j = jit::load_rec(params + (int64_t)n * jit::REC_WORDS);
+    if (!jit::has_contrast(j.ops)) return;  // the whole workgroup: the record is the frame's
+    constexpr int NP = VEC ? 4 : 1;
+    unsigned c[NP][3];
+    int64_t i0;
+    unsigned sum = 0;
+    if (jit_load<VEC>(src, n, blk, hw, c, i0)) {
+        jit::apply<NP, true>(j, 0, c);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) sum += jit::luma(c[p][0], c[p][1], c[p][2]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        atomicAdd(sums + n, (unsigned long long)wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3]);
+}
+
+// Pass 2: the whole list (contrast's mean from pass 1), norm1, the three planes.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_img_jitter_norm(const uint8_t *__restrict__ src, int64_t hw, int bpf,
+                                                         const uint32_t *__restrict__ params,
+                                                         const unsigned long long *__restrict__ sums, Norm nm,
+                                                         float *__restrict__ out) {
+    const int n = blockIdx.x / bpf, blk = blockIdx.x - n * bpf;
+    const jit::Rec j = jit::load_rec(params + (int64_t)n * jit::REC_WORDS);
+    constexpr int NP = VEC ? 4 : 1;
+    unsigned c[NP][3];
+    int64_t i0;
+    if (!jit_load<VEC>(src, n, blk, hw, c, i0)) return;
+    if (j.ops != 0) {
+        const int m = jit::has_contrast(j.ops) ? jit::contrast_mean(sums[n], hw) : 0;
+        jit::apply<NP, false>(j, m, c);
+    }
+    float *o = out + (int64_t)n * 3 * hw + i0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float m = nm.mean[k], s = nm.std[k];
+        if constexpr (VEC) {
+            const f32x4 v = {norm1(c[0][k], m, s), norm1(c[1][k], m, s), norm1(c[2][k], m, s), norm1(c[3][k], m, s)};
+            __builtin_nontemporal_store(v, (f32x4 *)(o + k * hw));
+        } else {
+            o[k * hw] = norm1(c[0][k], m, s);
+        }
+    }
+}
+
+// the geometry of a resize launch, shared by the fp32 and the uint8 entry
+struct RsLaunch {
+    RsAxis ax, ay;
+    int TH, rcap;
+    int64_t tiles_x, tiles_y, blocks;
+    size_t lds;
+};
+
+bool rs_launch(int N, int Hs, int Ws, int H, int W, RsLaunch *g) {
+    if (!rs_axis(Ws, W, &g->ax) || !rs_axis(Hs, H, &g->ay)) return false;
+    // the tallest tile whose source rows fit the intermediate: R <= (TH - 1) * scale + 2 * support + 1 <= rcap
+    g->TH = 16;
+    for (;; g->TH /= 2) {
+        g->rcap = (int)ceil((g->TH - 1) * g->ay.scale) + g->ay.ksize + 1;
+        if ((int64_t)g->rcap * RS_TW * 4 <= RS_INTER_BYTES || g->TH == 1) break;
+    }
+    g->tiles_x = (W + RS_TW - 1) / RS_TW;
+    g->tiles_y = (H + g->TH - 1) / g->TH;
+    g->blocks = g->tiles_x * g->tiles_y * N;
+    g->lds = 4 * ((size_t)g->rcap * RS_TW + (size_t)RS_TW * g->ax.ksize + (size_t)g->TH * g->ay.ksize + 2 * RS_TW +
+                  2 * g->TH);
+    return g->blocks <= 0x7fffffff;
+}
+
+template <bool U8>
+int rs_run(const uint8_t *src, int N, int Hs, int Ws, const void *plan_dev, int H, int W, const RsLaunch &g,
+           const Norm &nm, void *out, int vec, void *stream) {
+    const int32_t *xb = (const int32_t *)plan_dev, *xk = xb + 2 * (int64_t)W;
+    const int32_t *yb = xk + (int64_t)W * g.ax.ksize, *yk = yb + 2 * (int64_t)H;
+    const int64_t last_dw = ((int64_t)((uintptr_t)src & 3) + (int64_t)N * Hs * Ws * 3 - 1) >> 2;
+    // a window has at most ksize - 1 taps: up to 4, 8, 12 of them run unrolled (downscales up to 5.5x), more looped
+    auto kern = g.ax.ksize <= 5 ? k_img_resize_norm<1, U8> : g.ax.ksize <= 9 ? k_img_resize_norm<2, U8> :
+                g.ax.ksize <= 13 ? k_img_resize_norm<3, U8> : k_img_resize_norm<0, U8>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)g.blocks), dim3(256), g.lds, (hipStream_t)stream, src, Hs, Ws, H, W, xb, xk,
+                       yb, yk, g.ax.ksize, g.ay.ksize, g.TH, g.rcap, (int)g.tiles_x, (int)g.tiles_y, last_dw, nm, out,
+                       vec);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -364,30 +521,88 @@ extern "C" int bev_image_resize_normalize_u8_f32(const uint8_t *src, int N, int 
     RsAxis ax, ay;
     if (((uintptr_t)plan_dev & 3) || !rs_axis(Ws, W, &ax) || !rs_axis(Hs, H, &ay)) return BEV_ERR_ARGS;
     if (N == 0) return 0;
-    if (Hs == H && Ws == W) return bev_image_normalize_u8_f32(src, N, H, W, mean, stdv, out, stream);
-    // the tallest tile whose source rows fit the intermediate: R <= (TH - 1) * scale + 2 * support + 1 <= rcap
-    int TH = 16, rcap = 0;
-    for (;; TH /= 2) {
-        rcap = (int)ceil((TH - 1) * ay.scale) + ay.ksize + 1;
-        if ((int64_t)rcap * RS_TW * 4 <= RS_INTER_BYTES || TH == 1) break;
-    }
-    const int64_t tiles_x = (W + RS_TW - 1) / RS_TW, tiles_y = (H + TH - 1) / TH;
-    const int64_t blocks = tiles_x * tiles_y * N;
-    if (blocks > 0x7fffffff) return BEV_ERR_ARGS;
+    RsLaunch g;
+    if (!rs_launch(N, Hs, Ws, H, W, &g)) return BEV_ERR_ARGS;
     Norm nm;
     for (int c = 0; c < 3; ++c) {
         nm.mean[c] = mean[c];
         nm.std[c] = stdv[c];
     }
-    const int32_t *xb = (const int32_t *)plan_dev, *xk = xb + 2 * (int64_t)W;
-    const int32_t *yb = xk + (int64_t)W * ax.ksize, *yk = yb + 2 * (int64_t)H;
     const int vec = (W % 4 == 0) && (((uintptr_t)out & 15) == 0);
-    const int64_t last_dw = ((int64_t)((uintptr_t)src & 3) + (int64_t)N * Hs * Ws * 3 - 1) >> 2;
-    const size_t lds = 4 * ((size_t)rcap * RS_TW + (size_t)RS_TW * ax.ksize + (size_t)TH * ay.ksize + 2 * RS_TW + 2 * TH);
-    // a window has at most ksize - 1 taps: up to 4, 8, 12 of them run unrolled (downscales up to 5.5x), more looped
-    auto kern = ax.ksize <= 5 ? k_img_resize_norm<1> : ax.ksize <= 9 ? k_img_resize_norm<2> :
-                ax.ksize <= 13 ? k_img_resize_norm<3> : k_img_resize_norm<0>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, src, Hs, Ws, H, W, xb, xk, yb,
-                       yk, ax.ksize, ay.ksize, TH, rcap, (int)tiles_x, (int)tiles_y, last_dw, nm, out, vec);
+    return rs_run<false>(src, N, Hs, Ws, plan_dev, H, W, g, nm, out, vec, stream);
+}
+
+extern "C" int bev_image_resize_u8(const uint8_t *src, int N, int Hs, int Ws, const void *plan_dev, int H, int W,
+                                   uint8_t *out_u8, void *stream) {
+    if (!src || !plan_dev || !out_u8 || N < 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return BEV_ERR_ARGS;
+    RsAxis ax, ay;
+    if (((uintptr_t)plan_dev & 3) || !rs_axis(Ws, W, &ax) || !rs_axis(Hs, H, &ay)) return BEV_ERR_ARGS;
+    if (N == 0) return 0;
+    if (Hs == H && Ws == W)
+        return (int)hipMemcpyAsync(out_u8, src, (size_t)N * H * W * 3, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    RsLaunch g;
+    if (!rs_launch(N, Hs, Ws, H, W, &g)) return BEV_ERR_ARGS;
+    const int vec = (W % 4 == 0) && (((uintptr_t)out_u8 & 3) == 0);
+    return rs_run<true>(src, N, Hs, Ws, plan_dev, H, W, g, Norm{}, out_u8, vec, stream);
+}
+
+extern "C" int64_t bev_image_jitter_workspace_bytes(int N) { return N > 0 ? 8 * (int64_t)N : 0; }
+
+extern "C" int bev_image_jitter_normalize_u8_f32(const uint8_t *src, int N, int H, int W, const int32_t *params,
+                                                 const float *mean, const float *stdv, void *workspace,
+                                                 int64_t workspace_bytes, float *out, void *stream) {
+    if (!src || !params || !mean || !stdv || !workspace || !out || N < 0 || H <= 0 || W <= 0) return BEV_ERR_ARGS;
+    if (((uintptr_t)params & 3) || ((uintptr_t)workspace & 7) || ((uintptr_t)out & 3)) return BEV_ERR_ARGS;
+    if (workspace_bytes < bev_image_jitter_workspace_bytes(N)) return BEV_ERR_ARGS;
+    if (N == 0) return 0;
+    const int64_t hw = (int64_t)H * W;
+    const bool vec = (hw % 4 == 0) && (((uintptr_t)src & 3) == 0) && (((uintptr_t)out & 15) == 0);
+    const int64_t bpf = (hw + (vec ? 1024 : 256) - 1) / (vec ? 1024 : 256);
+    if (bpf * N > 0x7fffffff) return BEV_ERR_ARGS;
+    Norm nm;
+    for (int c = 0; c < 3; ++c) {
+        nm.mean[c] = mean[c];
+        nm.std[c] = stdv[c];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(workspace, 0, 8 * (size_t)N, st);
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid((unsigned)(bpf * N)), block(256);
+    const uint32_t *rec = (const uint32_t *)params;
+    unsigned long long *sums = (unsigned long long *)workspace;
+    if (vec) {
+        hipLaunchKernelGGL(k_img_jitter_sum<true>, grid, block, 0, st, src, hw, (int)bpf, rec, sums);
+        hipLaunchKernelGGL(k_img_jitter_norm<true>, grid, block, 0, st, src, hw, (int)bpf, rec, sums, nm, out);
+    } else {
+        hipLaunchKernelGGL(k_img_jitter_sum<false>, grid, block, 0, st, src, hw, (int)bpf, rec, sums);
+        hipLaunchKernelGGL(k_img_jitter_norm<false>, grid, block, 0, st, src, hw, (int)bpf, rec, sums, nm, out);
+    }
     return (int)hipGetLastError();
+}
+
+extern "C" int bev_image_jitter_u8_host(const uint8_t *src, int N, int H, int W, const int32_t *params,
+                                        uint8_t *out_u8) {
+    if (!src || !params || !out_u8 || N < 0 || H <= 0 || W <= 0 || ((uintptr_t)params & 3)) return BEV_ERR_ARGS;
+    const int64_t hw = (int64_t)H * W;
+    for (int n = 0; n < N; ++n) {
+        const jit::Rec j = jit::load_rec((const uint32_t *)params + (int64_t)n * jit::REC_WORDS);
+        const uint8_t *s = src + n * hw * 3;
+        uint8_t *o = out_u8 + n * hw * 3;
+        int m = 0;
+        if (jit::has_contrast(j.ops)) {
+            uint64_t sum = 0;
+            for (int64_t i = 0; i < hw; ++i) {
+                unsigned c[1][3] = {{s[3 * i], s[3 * i + 1], s[3 * i + 2]}};
+                jit::apply<1, true>(j, 0, c);
+                sum += jit::luma(c[0][0], c[0][1], c[0][2]);
+            }
+            m = jit::contrast_mean(sum, hw);
+        }
+        for (int64_t i = 0; i < hw; ++i) {
+            unsigned c[1][3] = {{s[3 * i], s[3 * i + 1], s[3 * i + 2]}};
+            jit::apply<1, false>(j, m, c);
+            for (int k = 0; k < 3; ++k) o[3 * i + k] = (uint8_t)c[0][k];
+        }
+    }
+    return 0;
 }

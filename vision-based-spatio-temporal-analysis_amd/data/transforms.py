@@ -25,11 +25,21 @@ bit-identical to `Normalize(ToTensor(Resize(img)))` (PIL's resize is integer ari
 fixed-point coefficients, which the kernel repeats).  Its host side is
 `build_transforms(img_size, normalize=False, resize=False)`: the deterministic ingest, which only
 decodes to uint8 HWC -- no `Resize`, and no `ColorJitter` either, drawing nothing from the RNG.
-The jitter cannot stay: in the reference it sits between `Resize` and `ToTensor`, so jittering the
-native-size frame before a device resize would produce a different image from the reference's
-(the enhancements are not linear in the pixels, and the resize rounds to uint8 before them).  The
-reference jitters at inference too (p = 0.5, the same transform for every split: a quirk), so this
-mode reproduces exactly the draws on which `RandomApply` skips the jitter.
+
+`resize_jitter_normalize_on_device` moves the jitter too, and with it the whole pipeline.  In the
+reference the jitter sits between `Resize` and `ToTensor` (and runs at inference as well, p = 0.5,
+the same transform for every split: a quirk), so it cannot run on the host in front of a device
+resize: the enhancements are not linear in the pixels, and the resize rounds to uint8 before them.
+What stays on the host is the random draws alone: `build_transforms(img_size, normalize=False,
+resize=False, jitter=True)` is `NativeSizeJitter`, which decodes the frame and draws as
+`RandomApply([ColorJitter])` does -- `torch.rand(1)`, then, only if the jitter applies,
+`ColorJitter.params_record()`: `randperm(4)` and one `uniform_` per factor -- so a seeded run
+leaves the global generator where the host pipeline leaves it, and returns the frame with an
+8-word record (the op order, the three factors as fp32 bits, the hue shift byte; all zero when
+the jitter is skipped).  On the device `bev_image_resize_u8` writes the resized uint8 frames and
+`bev_image_jitter_normalize_u8_f32` applies each frame's record -- PIL.ImageEnhance's blends and
+Pillow's RGB <-> HSV conversions restated operation for operation -- then ToTensor + Normalize:
+bit-identical to `Normalize(ToTensor(ColorJitter(Resize(img))))` on every draw.
 """
 from __future__ import annotations
 
@@ -43,7 +53,8 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 __all__ = ["build_transforms", "Compose", "Resize", "RandomApply", "ColorJitter", "ToTensor", "Normalize",
-           "ToUint8HWC", "normalize_on_device", "resize_normalize_on_device", "IMAGENET_MEAN", "IMAGENET_STD"]
+           "ToUint8HWC", "NativeSizeJitter", "normalize_on_device", "resize_normalize_on_device",
+           "jitter_normalize_on_device", "resize_jitter_normalize_on_device", "IMAGENET_MEAN", "IMAGENET_STD"]
 
 
 class Compose:
@@ -89,6 +100,11 @@ def _range(value: float, center: float = 1.0, bound=(0.0, float("inf"))) -> Tupl
     return max(lo, bound[0]), min(hi, bound[1])
 
 
+def _hue_shift_byte(hue_factor: float) -> np.ndarray:
+    """What torchvision adds to the HSV hue byte (uint8 wrap-around); also word 4 of a jitter record."""
+    return np.array(hue_factor * 255).astype(np.uint8)
+
+
 def _adjust_hue(img: Image.Image, hue_factor: float) -> Image.Image:
     if not -0.5 <= hue_factor <= 0.5:
         raise ValueError(f"hue_factor ({hue_factor}) is not in [-0.5, 0.5].")
@@ -98,7 +114,7 @@ def _adjust_hue(img: Image.Image, hue_factor: float) -> Image.Image:
     h, s, v = img.convert("HSV").split()
     np_h = np.array(h, dtype=np.uint8)
     with np.errstate(over="ignore"):
-        np_h += np.array(hue_factor * 255).astype(np.uint8)  # uint8 wrap-around, as torchvision
+        np_h += _hue_shift_byte(hue_factor)  # uint8 wrap-around, as torchvision
     h = Image.fromarray(np_h, "L")
     return Image.merge("HSV", (h, s, v)).convert(mode)
 
@@ -134,6 +150,36 @@ class ColorJitter:
         return img
 
 
+    def params_record(self) -> torch.Tensor:
+        """Draws exactly as `__call__` does and returns the draw as the device kernel's record, int32 [8]
+        (include/bev_mi355x.h): word 0 the enabled ops in the drawn order, four bits each (1 brightness, 2 contrast,
+        3 saturation, 4 hue; 0 ends the list); words 1-3 the three factors as fp32 bits (the float Pillow's blend
+        converts the Python double to); word 4 the hue shift byte; words 5-7 zero."""
+        fn_idx, b, c, s, h = self.get_params()
+        rec = np.zeros(8, dtype=np.int32)
+        ops = [fn_id + 1 for fn_id in fn_idx.tolist() if (b, c, s, h)[fn_id] is not None]
+        rec[0] = sum(code << (4 * i) for i, code in enumerate(ops))
+        rec[1:4] = np.array([1.0 if f is None else f for f in (b, c, s)], dtype=np.float32).view(np.int32)
+        rec[4] = 0 if h is None else int(_hue_shift_byte(h))
+        return torch.from_numpy(rec)
+
+
+class NativeSizeJitter:
+    """The host side of the device jitter: `RandomApply([jitter], p)` for a frame that is resized and jittered on the
+    GPU.  One `torch.rand(1)` per call as RandomApply, then (only if the jitter applies) the jitter's own draws;
+    returns the frame as [Hs, Ws, 3] uint8 with its int32 [8] record (all zero: not jittered)."""
+
+    def __init__(self, jitter: ColorJitter, p: float = 0.5):
+        self.jitter = jitter
+        self.p = float(p)
+
+    def __call__(self, img: Image.Image) -> Tuple[torch.Tensor, torch.Tensor]:
+        frame = ToUint8HWC()(img)
+        if self.p < torch.rand(1):
+            return frame, torch.zeros(8, dtype=torch.int32)
+        return frame, self.jitter.params_record()
+
+
 class ToUint8HWC:
     """PIL RGB image -> [H, W, 3] uint8 tensor (what ToTensor reads, before the float conversion)."""
 
@@ -158,17 +204,26 @@ class Normalize:
         return t.sub(self.mean).div(self.std)
 
 
-def build_transforms(img_size=(256, 256), normalize: bool = True, resize: bool = True) -> Compose:
+def _reference_jitter() -> ColorJitter:
+    return ColorJitter(brightness=0.2, contrast=0.2, saturation=0.2, hue=0.05)
+
+
+def build_transforms(img_size=(256, 256), normalize: bool = True, resize: bool = True, jitter: bool = False) -> Compose:
     """The reference pipeline (transforms.py:12-19).  normalize=False stops at uint8 HWC; resize=False (needs
-    normalize=False) only decodes to uint8 HWC at the frame's own size, without jitter (see module doc)."""
+    normalize=False) only decodes to uint8 HWC at the frame's own size, without jitter and without a draw; with
+    jitter=True (needs resize=False) it also makes the pipeline's draws and returns (frame, record) for
+    resize_jitter_normalize_on_device (see module doc)."""
+    if jitter and resize:
+        raise ValueError("build_transforms(jitter=True) asks for the draws of the device jitter: it requires "
+                         "resize=False (with resize=True the jitter runs on the host, as always)")
     if not resize:
         if normalize:
             raise ValueError("build_transforms(resize=False) hands native-size uint8 frames to "
                              "resize_normalize_on_device: it requires normalize=False")
-        return Compose([ToUint8HWC()])
+        return Compose([NativeSizeJitter(_reference_jitter(), p=0.5) if jitter else ToUint8HWC()])
     steps: List[Callable] = [
         Resize(img_size),
-        RandomApply([ColorJitter(brightness=0.2, contrast=0.2, saturation=0.2, hue=0.05)], p=0.5),
+        RandomApply([_reference_jitter()], p=0.5),
     ]
     steps += [ToTensor(), Normalize(IMAGENET_MEAN, IMAGENET_STD)] if normalize else [ToUint8HWC()]
     return Compose(steps)
@@ -202,4 +257,46 @@ def resize_normalize_on_device(images_u8: torch.Tensor, img_size, mean=IMAGENET_
     H, W = int(img_size[0]), int(img_size[1])
     flat = images_u8.reshape(-1, Hs, Ws, 3)
     out = nat.image_resize_normalize_u8(flat, (H, W), mean, std)
+    return out.view(*lead, 3, H, W)
+
+
+def _flat_params(params: torch.Tensor, lead) -> torch.Tensor:
+    if tuple(params.shape) != tuple(lead) + (8,):
+        raise ValueError(f"jitter records must be int32 {tuple(lead) + (8,)}, got {tuple(params.shape)}")
+    return params.reshape(-1, 8)
+
+
+def jitter_normalize_on_device(images_u8: torch.Tensor, params: torch.Tensor, mean=IMAGENET_MEAN,
+                               std=IMAGENET_STD) -> torch.Tensor:
+    """[B, V, H, W, 3] (or [N, H, W, 3]) uint8 on the GPU, already at the output size, and the frames' jitter records
+    [B, V, 8] (or [N, 8]) int32, on the CPU or the GPU -> [B, V, 3, H, W] fp32 ColorJitter + ToTensor + Normalize.
+
+    HIP kernels of `bev_image_jitter_normalize_u8_f32`; bit-identical to the CPU transforms with the same draws.
+    """
+    import bev_native as nat
+
+    lead = images_u8.shape[:-3]
+    H, W = images_u8.shape[-3], images_u8.shape[-2]
+    out = nat.image_jitter_normalize_u8(images_u8.reshape(-1, H, W, 3), _flat_params(params, lead), mean, std)
+    return out.view(*lead, 3, H, W)
+
+
+def resize_jitter_normalize_on_device(images_u8: torch.Tensor, img_size, params: torch.Tensor, mean=IMAGENET_MEAN,
+                                      std=IMAGENET_STD) -> torch.Tensor:
+    """[B, V, Hs, Ws, 3] (or [N, Hs, Ws, 3]) uint8 on the GPU, at the frames' native size, and the frames' jitter
+    records [B, V, 8] (or [N, 8]) int32 (the batch's "jitter" of WildtrackDataset(native_size=True, jitter=True)), on
+    the CPU or the GPU -> [B, V, 3, H, W] fp32: the reference's whole transform, Resize(img_size) +
+    RandomApply(ColorJitter) + ToTensor + Normalize with the draws the records hold.
+
+    `bev_image_resize_u8` (the resized uint8 frames), then `bev_image_jitter_normalize_u8_f32`; bit-identical to the
+    CPU pipeline on PIL.  A downscale of more than 17x per axis is refused.
+    """
+    import bev_native as nat
+
+    lead = images_u8.shape[:-3]
+    Hs, Ws = images_u8.shape[-3], images_u8.shape[-2]
+    H, W = int(img_size[0]), int(img_size[1])
+    flat_params = _flat_params(params, lead)
+    resized = nat.image_resize_u8(images_u8.reshape(-1, Hs, Ws, 3), (H, W))
+    out = nat.image_jitter_normalize_u8(resized, flat_params, mean, std)
     return out.view(*lead, 3, H, W)

@@ -25,8 +25,11 @@ as one batch (float32 matmul, equal to the per-point product within fp32 roundin
 `images_uint8=True` makes __getitem__ return [V, H, W, 3] uint8 for on-device normalisation
 (`data.transforms.normalize_on_device`); `native_size=True` (implies uint8) returns the decoded frames at their own
 size, [V, Hs, Ws, 3], with no Resize and no ColorJitter, for `data.transforms.resize_normalize_on_device` (the
-deterministic ingest; data/transforms.py says why the jitter cannot stay).  Frames of one dataset share a size, as
-Wildtrack's do, so `collate_fn` stacks them unchanged.
+deterministic ingest); `native_size=True, jitter=True` also makes the pipeline's random draws per frame
+(RandomApply's, then ColorJitter's, from torch's global generator in the host pipeline's order) and returns them as
+"jitter", int32 [V, 8] records (stacked to [B, V, 8] by `collate_fn`), for
+`data.transforms.resize_jitter_normalize_on_device`: the reference's whole transform on the device, bit for bit.
+Frames of one dataset share a size, as Wildtrack's do, so `collate_fn` stacks them unchanged.
 
 Not on the hot path: this is host I/O that feeds it (JPEG/PNG decode in DataLoader workers).
 """
@@ -316,7 +319,11 @@ def _frame_centres(data: Any, H_i2w: List[torch.Tensor]) -> List[List[float]]:
 class WildtrackDataset(torch.utils.data.Dataset):
     """Multi-view Wildtrack frames (wildtrack_loader.py:250-386)."""
 
-    def __init__(self, cfg: Dict[str, Any], images_uint8: bool = False, native_size: bool = False):
+    def __init__(self, cfg: Dict[str, Any], images_uint8: bool = False, native_size: bool = False,
+                 jitter: bool = False):
+        if jitter and not native_size:
+            raise ValueError("WildtrackDataset(jitter=True) returns the draws of the device jitter: it requires "
+                             "native_size=True (the other modes jitter on the host)")
         self.cfg = cfg
         self.data_root = Path(cfg["DATA"]["DATA_ROOT"]).resolve()
         self.views = int(cfg["DATA"]["VIEWS"])
@@ -324,8 +331,9 @@ class WildtrackDataset(torch.utils.data.Dataset):
         self.img_size = (int(H), int(W))
         self.native_size = bool(native_size)
         self.images_uint8 = bool(images_uint8) or self.native_size
+        self.jitter = bool(jitter)
         self.transform = build_transforms(img_size=self.img_size, normalize=not self.images_uint8,
-                                          resize=not self.native_size)
+                                          resize=not self.native_size, jitter=self.jitter)
         wh = cfg.get("LOSS", {}).get("DEFAULT_BOX_WH", [0.6, 0.6])
         self.default_box_wh = (float(wh[0]), float(wh[1]))
 
@@ -389,25 +397,35 @@ class WildtrackDataset(torch.utils.data.Dataset):
             })
 
     def __getitem__(self, idx: int) -> Dict[str, Any]:
-        imgs, paths = [], []
+        imgs, records, paths = [], [], []
         for v in range(self.views):
             p = self.cam_dirs[v] / self.frame_files[idx]
-            imgs.append(self.transform(Image.open(p).convert("RGB")))
+            x = self.transform(Image.open(p).convert("RGB"))
+            if self.jitter:
+                x, rec = x
+                records.append(rec)
+            imgs.append(x)
             paths.append(str(p))
         calib = {"intrinsic": self.intrinsics[idx], "extrinsic": self.extrinsics[idx]}
         targets = self.targets_per_frame[idx] if idx < len(self.targets_per_frame) else {
             "boxes_world": torch.zeros(0, 4), "centers_world": torch.zeros(0, 2), "keypoints": None, "calib": calib}
-        return {"images": torch.stack(imgs, dim=0), "calib": calib, "targets": targets,
+        item = {"images": torch.stack(imgs, dim=0), "calib": calib, "targets": targets,
                 "meta": {"frame_idx": int(idx), "paths": paths}}
+        if self.jitter:
+            item["jitter"] = torch.stack(records, dim=0)
+        return item
 
 
 def collate_fn(batch: List[Dict[str, Any]]) -> Dict[str, Any]:
     """Stack images to [B, V, ...]; calibrations as List[List[Tensor]] (wildtrack_loader.py:389-401)."""
     batch = [b for b in batch if b is not None]
-    return {
+    out = {
         "images": torch.stack([b["images"] for b in batch], dim=0),
         "calib": {"intrinsic": [b["calib"]["intrinsic"] for b in batch],
                   "extrinsic": [b["calib"]["extrinsic"] for b in batch]},
         "targets": [b["targets"] for b in batch],
         "meta": [b["meta"] for b in batch],
     }
+    if batch and "jitter" in batch[0]:  # the device jitter's records, [B, V, 8]
+        out["jitter"] = torch.stack([b["jitter"] for b in batch], dim=0)
+    return out
