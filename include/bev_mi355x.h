@@ -490,6 +490,33 @@ int bev_l1_losses_bwd_f32(const float *offset, const float *size, int B, int64_t
 int bev_gaussian_radius_f32(const float *width_cells, const float *height_cells, int n, float f_1mov,
                             float rcp_1pov, float f_4ov, float f_m2ov, float f_ovm1, int ov_zero, float min_radius,
                             int64_t *radius, void *stream);
+/* CenterNet training targets of model_wrapper.py:126-203, 278-300 (BEVNet._build_training_targets, as torch's float32
+ * ops compute them on the device) in two launches: boxes [N][4] (cx, cy, w, h in world units), frame [N] int64.  Per
+ * frame b in [0, B) the boxes with frame[i] == b whose centre is inside the grid (0 <= gx < Wb, 0 <= gy < Hb, gx =
+ * (cx - x_min) * rcp_res_x) are taken in array order and the first M fill the slots: indices [B][M] int64 = floor(gy)
+ * Wb + floor(gx), mask [B][M] = 1, offset [B][M][2] = the fractions of (gx, gy), size_log [B][M][2] = log of the size
+ * in cells (clamped to >= 1e-3); every other slot is written 0.  heatmap [B][1][Hb][Wb] = per cell the maximum over
+ * the frame's slotted objects with radius > 0 of exp(-(dx^2 + dy^2) / 2 sigma^2), |dx| <= r and |dy| <= r, sigma =
+ * (2 r + 1) / 6, else 0; r is bev_gaussian_radius_f32's (the same constants).  Every output element is stored exactly
+ * once (no memset, no atomics, deterministic); any radius is accepted, a window larger than the map covers the map.
+ * A frame value outside [0, B) names no frame: the box is ignored.  rcp_res_x, rcp_res_y: the reciprocals of the cell
+ * size as torch's device division by a host scalar forms them, (float)(1.0 / res).  workspace: 16-byte aligned, >= bev_centernet_targets_workspace_bytes(B, M) bytes (0 for a refused B, M).
+ * Checked on the host before any launch: BEV_ERR_ARGS for a null pointer (boxes / frame may be null when N == 0, the
+ * slot outputs when B * M == 0), a negative N, B or M, a non-positive Hb or Wb, Hb * Wb > 2^28, B * M > 2^24 or a
+ * workspace that is too small.  B == 0 is a no-op; N == 0 writes all-zero targets. */
+int64_t bev_centernet_targets_workspace_bytes(int B, int M);
+int bev_centernet_targets_f32(const float *boxes, const int64_t *frame, int N, int B, int M, int Hb, int Wb,
+                              float x_min, float y_min, float rcp_res_x, float rcp_res_y, float f_1mov, float rcp_1pov,
+                              float f_4ov, float f_m2ov, float f_ovm1, int ov_zero, float min_radius, float *heatmap,
+                              int64_t *indices, float *mask, float *offset, float *size_log, void *workspace,
+                              int64_t workspace_bytes, void *stream);
+/* The same targets (model_wrapper.py:126-203, 278-300) on the CPU from host pointers: the kernels' per-object
+ * functions compiled for the host, no HIP call, no workspace.  log / exp are the host's libm (within 1 ulp of the
+ * device's); everything else is bit-identical.  The same argument checks. */
+int bev_centernet_targets_host(const float *boxes, const int64_t *frame, int N, int B, int M, int Hb, int Wb,
+                               float x_min, float y_min, float rcp_res_x, float rcp_res_y, float f_1mov,
+                               float rcp_1pov, float f_4ov, float f_m2ov, float f_ovm1, int ov_zero, float min_radius,
+                               float *heatmap, int64_t *indices, float *mask, float *offset, float *size_log);
 int64_t bev_focal_loss_workspace_bytes(int64_t n);
 int bev_focal_loss_fwd_f32(const float *logits, const float *gt, int64_t n, float alpha, float beta, float *loss,
                            float *inv_norm, void *workspace, int64_t workspace_bytes, void *stream);

@@ -1,6 +1,6 @@
 """Training-step timing (BASELINE config 3 shape, one GPU): ResNet-50 trunk + proj -> IPM warp -> head.
 
-    python tools/train_step_bench.py [--steps 5] [--bevnet] [--amp] [--fp32-kernels]
+    python tools/train_step_bench.py [--steps 5] [--bevnet] [--amp] [--fp32-kernels] [--torch-targets | --ab-targets R]
 
 Default: the hot path alone -- CNNEncoder (trunk trainable, native forward + backward) -> fused warp
 + mean (native forward + backward) -> sum(out * r) -> Adam step.  --bevnet: the full BEVNet (encoder,
@@ -36,6 +36,10 @@ def main():
     ap.add_argument("--no-mask-bytes", action="store_true", help="A/B: bn3's backward re-reads the fp32 block output "
                     "instead of the forward's ReLU mask bytes (trunk_grad.RELU_MASK_BYTES)")
     ap.add_argument("--torch-loss", action="store_true", help="A/B: the focal and L1 losses as torch ops")
+    ap.add_argument("--torch-targets", action="store_true", help="A/B: the CenterNet targets as torch ops "
+                    "(model_wrapper.NATIVE_TARGETS off)")
+    ap.add_argument("--ab-targets", type=int, default=0, metavar="ROUNDS", help="A/B in one process: ROUNDS times a "
+                    "native-targets run then a torch-targets run of --steps steps each, one JSON line per run")
     ap.add_argument("--eager-decode", action="store_true", help="A/B: BEVNet.forward synchronises on its decode")
     ap.add_argument("--loss-graph", action="store_true", help="A/B: BEVNet.loss as a replayed graph pair "
                     "(model_wrapper.LOSS_GRAPHS)")
@@ -55,6 +59,7 @@ def main():
     import models.model_wrapper as _mw
     _mw.LAZY_DECODE = not a.eager_decode
     _mw.NATIVE_LOSS = not a.torch_loss
+    _mw.NATIVE_TARGETS = not a.torch_targets
     _mw.LOSS_GRAPHS = a.loss_graph
     for kv in a.tune:
         name, v = kv.split("=")
@@ -119,21 +124,33 @@ def main():
             return loss
     for _ in range(a.warmup):
         step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        loss = step()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / a.steps
-    print(json.dumps({"what": "bevnet train step" if a.bevnet else "hot-path train step", "backbone": a.backbone,
-                      "tune": a.tune, "bev": [480, 1440], "cameras": V, "img": [H, W], "feat_dim": 64,
-                      "bev_proj_ch": a.proj_ch if a.bevnet else None,
-                      "amp": a.amp, "half_convs": a.amp and not a.fp32_kernels,
-                      "decode": "eager" if a.eager_decode else "lazy", "loss_impl": "torch" if a.torch_loss else "native",
-                      "targets": "device" if a.device_targets else "host",
-                      "ms_per_step": round(dt * 1e3, 2), "frames_per_s": round(1.0 / dt, 3),
-                      "loss": float(loss)}), flush=True)
 
+    def run(native_targets: bool):
+        _mw.NATIVE_TARGETS = native_targets
+        step()  # the arm's own first step (workspace, allocator) stays out of the timing
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            loss = step()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / a.steps
+        print(json.dumps({"what": "bevnet train step" if a.bevnet else "hot-path train step", "backbone": a.backbone,
+                          "tune": a.tune, "bev": [480, 1440], "cameras": V, "img": [H, W], "feat_dim": 64,
+                          "bev_proj_ch": a.proj_ch if a.bevnet else None,
+                          "amp": a.amp, "half_convs": a.amp and not a.fp32_kernels,
+                          "decode": "eager" if a.eager_decode else "lazy",
+                          "loss_impl": "torch" if a.torch_loss else "native",
+                          "targets_impl": "native" if native_targets else "torch",
+                          "targets": "device" if a.device_targets else "host",
+                          "ms_per_step": round(dt * 1e3, 2), "frames_per_s": round(1.0 / dt, 3),
+                          "loss": float(loss)}), flush=True)
+
+    if a.ab_targets:
+        for _ in range(a.ab_targets):
+            run(True)
+            run(False)
+    else:
+        run(not a.torch_targets)
 
 if __name__ == "__main__":
     main()

@@ -61,6 +61,11 @@ SIGNATURES = {
     "bev_l1_losses_fwd_f32": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "bev_l1_losses_bwd_f32": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "bev_gaussian_radius_f32": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
+    "bev_centernet_targets_workspace_bytes": (_i64, [_i, _i]),
+    "bev_centernet_targets_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _i64, _vp]),
+    "bev_centernet_targets_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp,
+                                        _vp, _vp, _vp, _vp]),
     "bev_focal_loss_workspace_bytes": (_i64, [_i64]),
     "bev_focal_loss_fwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "bev_focal_loss_bwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
@@ -1819,16 +1824,93 @@ def l1_losses_bwd(offset, size, indices, mask, off_t, size_t, grad_losses, fwd_o
 def gaussian_radius(width_cells: torch.Tensor, height_cells: torch.Tensor, overlap: float, min_radius: int):
     """BEVNet._gaussian_radius_tensor (model_wrapper.py:205-233) in one launch, the same float32 values as torch's ops
     on the device -> int64 radii."""
-    import numpy as np
     w, h = width_cells.contiguous(), height_cells.contiguous()
     _require_gpu(w, h)
     out = torch.empty(w.shape, device=w.device, dtype=torch.int64)
-    f32 = np.float32
-    _check(lib().bev_gaussian_radius_f32(_ptr(w), _ptr(h), w.numel(), float(f32(1 - overlap)),
-                                         float(f32(1.0) / f32(1 + overlap)), float(f32(4 * overlap)),
-                                         float(f32(-2 * overlap)), float(f32(overlap - 1)), int(overlap == 0),
-                                         float(min_radius), _ptr(out), _stream(w)), "bev_gaussian_radius_f32")
+    _check(lib().bev_gaussian_radius_f32(_ptr(w), _ptr(h), w.numel(), *_radius_scalars(overlap, min_radius), _ptr(out),
+                                         _stream(w)), "bev_gaussian_radius_f32")
     return out
+
+
+def _radius_scalars(overlap: float, min_radius):
+    """bev_gaussian_radius_f32's constants: the Python-scalar operands of the radius formula as float32."""
+    import numpy as np
+    f32 = np.float32
+    return (float(f32(1 - overlap)), float(f32(1.0) / f32(1 + overlap)), float(f32(4 * overlap)),
+            float(f32(-2 * overlap)), float(f32(overlap - 1)), int(overlap == 0), float(min_radius))
+
+
+def _targets_scalars(bounds, res, overlap: float, min_radius):
+    """The Python-scalar operands of the target arithmetic (include/bev_mi355x.h): x_min, y_min, the reciprocals of
+    res_x / res_y and the radius constants.  torch's device division of a float32 tensor by a Python scalar s is a
+    product with (float)(1.0 / s), the reciprocal taken in double (measured on the device against the float and the
+    true-division forms: profiles/r21a_scalar_division_forms.txt)."""
+    import numpy as np
+    f32 = np.float32
+    return (float(f32(bounds[0])), float(f32(bounds[2])), float(f32(1.0 / float(res[0]))),
+            float(f32(1.0 / float(res[1])))) + _radius_scalars(overlap, min_radius)
+
+
+_TARGETS_WS = {}  # (B, M, device) -> the kernels' object-list workspace (reused: launches on a stream are ordered)
+
+
+def centernet_targets(boxes: torch.Tensor, frame: torch.Tensor, B: int, M: int, bev_hw, bounds, res, overlap: float,
+                      min_radius):
+    """BEVNet's CenterNet training targets (model_wrapper.py:126-203, 278-300) in two launches, no synchronisation:
+    boxes [N, 4] fp32 (cx, cy, w, h, world units) and frame [N] int64 on the GPU; bev_hw = (Hb, Wb), bounds = (x_min,
+    x_max, y_min, y_max), res = (res_x, res_y) -> heatmap [B, 1, Hb, Wb], indices [B, M] int64, mask [B, M], offset
+    [B, M, 2], size_log [B, M, 2]: the first M in-grid boxes of each frame fill its slots in array order; the same
+    float32 values as BEVNet._targets_from_boxes' torch ops on the device.  Any radius (no window tensor)."""
+    boxes, frame = boxes.contiguous(), frame.contiguous()
+    _require_gpu(boxes)
+    _require_gpu(frame, dtypes=(torch.int64,), what="int64")
+    N = boxes.shape[0]
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or tuple(frame.shape) != (N,) or frame.device != boxes.device:
+        raise ValueError(f"centernet_targets expects boxes [N, 4] and frame [N] on one device, got "
+                         f"{tuple(boxes.shape)} {tuple(frame.shape)}")
+    B, M, (Hb, Wb) = int(B), int(M), (int(v) for v in bev_hw)
+    dev = boxes.device
+    L = lib()
+    nbytes = int(L.bev_centernet_targets_workspace_bytes(B, M))
+    key = (B, M, dev)
+    ws = _TARGETS_WS.get(key)
+    if ws is None:
+        ws = _TARGETS_WS[key] = torch.empty(max(nbytes // 16, 1), 2, device=dev, dtype=torch.int64)
+    hm = torch.empty(B, 1, Hb, Wb, device=dev)
+    indices = torch.empty(B, M, device=dev, dtype=torch.int64)
+    mask = torch.empty(B, M, device=dev)
+    offset = torch.empty(B, M, 2, device=dev)
+    size_log = torch.empty(B, M, 2, device=dev)
+    _check(L.bev_centernet_targets_f32(_ptr(boxes), _ptr(frame), N, B, M, Hb, Wb,
+                                       *_targets_scalars(bounds, res, overlap, min_radius), _ptr(hm), _ptr(indices),
+                                       _ptr(mask), _ptr(offset), _ptr(size_log), _ptr(ws), nbytes, _stream(boxes)),
+           "bev_centernet_targets_f32")
+    return hm, indices, mask, offset, size_log
+
+
+def centernet_targets_host(boxes, frame, B: int, M: int, bev_hw, bounds, res, overlap: float, min_radius):
+    """centernet_targets on the CPU (bev_centernet_targets_host: the kernels' per-object functions compiled for the
+    host; no GPU needed): boxes [N, 4] float32 and frame [N] int64 numpy arrays -> the five numpy arrays.  The way to
+    check the slotting and the arithmetic without a device."""
+    import numpy as np
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+    frame = np.ascontiguousarray(frame, dtype=np.int64)
+    N = boxes.shape[0]
+    if boxes.ndim != 2 or boxes.shape[1] != 4 or frame.shape != (N,):
+        raise ValueError(f"centernet_targets_host expects boxes [N, 4] and frame [N], got {boxes.shape} {frame.shape}")
+    B, M, (Hb, Wb) = int(B), int(M), (int(v) for v in bev_hw)
+    if B < 0 or M < 0 or Hb <= 0 or Wb <= 0:
+        raise ValueError(f"centernet_targets_host: bad sizes B={B} M={M} bev_hw=({Hb}, {Wb})")
+    hm = np.empty((B, 1, Hb, Wb), np.float32)
+    indices = np.empty((B, M), np.int64)
+    mask = np.empty((B, M), np.float32)
+    offset = np.empty((B, M, 2), np.float32)
+    size_log = np.empty((B, M, 2), np.float32)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)  # noqa: E731
+    _check(lib().bev_centernet_targets_host(p(boxes), p(frame), N, B, M, Hb, Wb,
+                                            *_targets_scalars(bounds, res, overlap, min_radius), p(hm), p(indices),
+                                            p(mask), p(offset), p(size_log)), "bev_centernet_targets_host")
+    return hm, indices, mask, offset, size_log
 
 
 DECODE_SORT_CHUNK = 8192  # keys per LDS chunk of the large-path sort (bev_decode.hip SORT_CHUNK)

@@ -17,8 +17,9 @@ The computation is reorganised for the GPU:
   to fp32 reassociation (the BEVNet parity test pins it against the reference's own outputs).
 * The head input is assembled channels-last ([B, Hb, Wb, ceil32(P+2)], ceil64 for the "f16" inference head:
   projection, pos-enc, zero pad) and fed to BEVDetector.forward_nhwc; `bev_feat` is returned as an NCHW view of it.
-* Training targets are built for the whole batch at once (no per-object Python loop / host syncs): gaussian
-  splats are one scatter_reduce('amax') over every object's footprint.
+* Training targets are built for the whole batch at once (no per-object Python loop / host syncs): on the GPU by
+  two native launches (NATIVE_TARGETS: bev_native.centernet_targets), else as torch ops whose gaussian splats are
+  one scatter_reduce('amax') over every object's footprint.
 """
 import math
 from typing import Any, Dict, List, Optional, Tuple
@@ -48,6 +49,11 @@ LAZY_DECODE = True
 # BEVNet's focal heatmap and L1 offset / size losses on the GPU run on the native kernels (A/B:
 # tools/train_step_bench.py --torch-loss)
 NATIVE_LOSS = True
+
+# BEVNet's CenterNet targets for boxes on the GPU are built by the native kernels (bev_native.centernet_targets: two
+# launches instead of ~40 torch ops, no radius bound, no window tensor, no host synchronisation for device-resident
+# boxes; the same float32 values as the torch ops below).  A/B: tools/train_step_bench.py --torch-targets
+NATIVE_TARGETS = True
 
 # BEVNet.loss in a training step replays the target construction + loss terms as one captured graph pair
 # (torch.cuda.make_graphed_callables): ~50 small launches become two graph launches, so the loss no longer waits on
@@ -417,6 +423,11 @@ class BEVNet(nn.Module):
     def _targets_from_boxes(self, boxes, frame, bound: Optional[int], B: int) -> Dict[str, torch.Tensor]:
         dev = next(self.parameters()).device
         M, Hb, Wb = self.max_objects, self.bev_h, self.bev_w
+        if NATIVE_TARGETS and boxes.is_cuda:  # the same float32 op sequence in two launches; needs no `bound`
+            hm, indices, mask, offset, size_log = _nat.centernet_targets(
+                boxes, frame, B, M, (Hb, Wb), self.bounds, (self.res_x, self.res_y), self.gaussian_iou,
+                self.gaussian_min_radius)
+            return {"heatmap": hm, "indices": indices, "mask": mask, "offset": offset, "size_log": size_log}
         hm_ext = torch.zeros(B * Hb * Wb + 1, device=dev)  # + one discarded cell
         hm = hm_ext[:-1].view(B, 1, Hb, Wb)
         if boxes.shape[0] == 0:
