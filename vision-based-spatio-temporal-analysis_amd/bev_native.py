@@ -1707,6 +1707,7 @@ def decode(heatmap: torch.Tensor, offset: torch.Tensor, size: torch.Tensor, boun
     """heatmap [B,1,H,W], offset / size [B,2,H,W] (device) -> (boxes list of [K,4], scores list of [K]).
     Like the reference there is no candidate limit: a frame with more candidates than the LDS sort holds
     (bev_decode_max_candidates) is finished by the global-memory sort + blocked NMS (bev_decode_nms_large_f32).
+    nms_dist is compared as the reference compares it, as a double (`radius` below).
     One host synchronisation per batch (two when some frame needs the large path).  lazy: return two
     DetectionList sequences instead; the synchronisation happens when one of them is first read."""
     heatmap, offset, size = heatmap.contiguous().float(), offset.contiguous().float(), size.contiguous().float()
@@ -1725,7 +1726,12 @@ def decode(heatmap: torch.Tensor, offset: torch.Tensor, size: torch.Tensor, boun
     boxes = torch.empty(B, cap, 4, device=dev, dtype=torch.float32)
     scores = torch.empty(B, cap, device=dev, dtype=torch.float32)
     nk = torch.empty(B, device=dev, dtype=torch.int32)
-    args = (float(x_min), float(y_min), float(res_x), float(res_y), float(nms_dist))
+    # detector.py:116 compares torch.norm(...).item(), a double holding the fp32 distance, with the double nms_dist_m:
+    # for an fp32 distance d, d < nms_dist exactly when d < the smallest fp32 that is >= nms_dist
+    radius = torch.tensor(float(nms_dist), dtype=torch.float32)
+    if float(radius) < float(nms_dist):
+        radius = torch.nextafter(radius, torch.tensor(float("inf")))
+    args = (float(x_min), float(y_min), float(res_x), float(res_y), float(radius))
     _check(lib().bev_decode_nms_f32(_ptr(idx), _ptr(sc), _ptr(cnt), B, cap, _ptr(offset), _ptr(size), H, W, *args,
                                     _ptr(boxes), _ptr(scores), _ptr(nk), st), "bev_decode_nms_f32")
     kc = torch.empty(2, B, dtype=torch.int32, pin_memory=True)

@@ -55,11 +55,25 @@ __global__ void k_decode_peaks(const float *__restrict__ heat, int H, int W, flo
     }
 }
 
-// ascending 64-bit key = descending score, then ascending cell index
+// ascending 64-bit key = descending score (IEEE order: -0.0 == +0.0, as torch.argsort compares), then ascending
+// cell index.  Bits 63..32: the score's order-reversed monotone image, a zero of either sign as +0.0; bits 31..1:
+// the cell index (< 2^31); bit 0: set when the score is -0.0, so that key_score returns the candidate's own
+// bits.  Cell indices are unique within a frame: bit 0 never decides an order.
 __device__ __forceinline__ uint64_t sort_key(float s, int32_t idx) {
     uint32_t u = __float_as_uint(s);
+    const uint32_t neg_zero = (u == 0x80000000u) ? 1u : 0u;
+    u = neg_zero ? 0u : u;
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone float -> uint
-    return ((uint64_t)(~u) << 32) | (uint32_t)idx;
+    return ((uint64_t)(~u) << 32) | ((uint32_t)idx << 1) | neg_zero;
+}
+
+__device__ __forceinline__ int32_t key_cell(uint64_t key) { return (int32_t)((uint32_t)key >> 1); }
+
+// score = hm[mask]: the candidate's own score bits
+__device__ __forceinline__ float key_score(uint64_t key) {
+    uint32_t u = ~(uint32_t)(key >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __uint_as_float((key & 1u) ? 0x80000000u : u);
 }
 
 __global__ __launch_bounds__(NMS_THREADS) void k_decode_nms(
@@ -102,7 +116,7 @@ __global__ __launch_bounds__(NMS_THREADS) void k_decode_nms(
     float *bo = boxes + (size_t)b * cap * 4;
     float *so = scores + (size_t)b * cap;
     for (int i = 0; i < K; ++i) {
-        const int32_t c = (int32_t)(keys[i] & 0xffffffffu);
+        const int32_t c = key_cell(keys[i]);
         const int y = c / W, x = c - y * W;
         // detector.py:103-108, fp32 op by op: x_min + (xs.float() + off_x) * res_x, ...
         const float cx = x_min + ((float)x + ob[c]) * res_x;
@@ -124,10 +138,7 @@ __global__ __launch_bounds__(NMS_THREADS) void k_decode_nms(
             bo[4 * n + 1] = cy;
             bo[4 * n + 2] = sb[c] * res_x;
             bo[4 * n + 3] = sb[plane + c] * res_y;
-            // score = hm[mask]: the candidate's peak value (the key's score bits)
-            uint32_t u = ~(uint32_t)(keys[i] >> 32);
-            u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-            so[n] = __uint_as_float(u);
+            so[n] = key_score(keys[i]);
             nk = n + 1;
         }
         __syncthreads();
@@ -232,7 +243,7 @@ __global__ __launch_bounds__(NMS_L_THREADS) void k_large_nms(
         int32_t c = 0;
         if (i < K) {
             key = kb[i];
-            c = (int32_t)(key & 0xffffffffu);
+            c = key_cell(key);
             const int y = c / W, x = c - y * W;
             cx = x_min + ((float)x + ob[c]) * res_x;
             cy = y_min + ((float)y + ob[plane + c]) * res_y;
@@ -283,9 +294,7 @@ __global__ __launch_bounds__(NMS_L_THREADS) void k_large_nms(
                 bo[4 * slot + 1] = cy;
                 bo[4 * slot + 2] = sb[c] * res_x;
                 bo[4 * slot + 3] = sb[plane + c] * res_y;
-                uint32_t u = ~(uint32_t)(key >> 32);
-                u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-                so[slot] = __uint_as_float(u);
+                so[slot] = key_score(key);
             }
             if (lane == 0) nk_s = n + __builtin_popcountll(kept);
         }

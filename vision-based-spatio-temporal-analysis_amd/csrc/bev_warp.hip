@@ -1254,7 +1254,10 @@ __global__ __launch_bounds__(FT_NT, v2_occ(MODE)) void k_warp_fuse_v2(
 
         int nview = 0;  // live views done (timing stamps)
         for (int v = v_first, vn; v < V; v = vn) {
-            vn = next_live(v);
+            // the skipped views after v take their max(acc, 0) AFTER view v's sample, in view order: torch.max keeps
+            // the first of a -0 / +0 tie
+            if constexpr (MODE == BEV_FUSE_MAX) vn = peek_live(v);
+            else vn = next_live(v);
             Box bx = bn;
             const int off = offn;
             [[maybe_unused]] const int bytesc = bytesn;  // SPAN only, as bytesn / spsn: this view's image
@@ -1400,6 +1403,8 @@ __global__ __launch_bounds__(FT_NT, v2_occ(MODE)) void k_warp_fuse_v2(
             } else if (empty) {
                 zero_view<MODE>(acc, v);
             }
+            if constexpr (MODE == BEV_FUSE_MAX)
+                for (int u = v + 1; u < vn; ++u) zero_view<MODE>(acc, u);
             STAMP_VIEW(nview, 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of view v+1 landed
             __syncthreads();  // all of it landed; image of view v and red[] are free
