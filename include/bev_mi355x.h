@@ -517,6 +517,30 @@ int bev_centernet_targets_host(const float *boxes, const int64_t *frame, int N, 
                                float x_min, float y_min, float rcp_res_x, float rcp_res_y, float f_1mov,
                                float rcp_1pov, float f_4ov, float f_m2ov, float f_ovm1, int ov_zero, float min_radius,
                                float *heatmap, int64_t *indices, float *mask, float *offset, float *size_log);
+/* Validation scoring of train.py:78-104 (compute_metrics) for a batch in one launch, no host synchronisation.
+ * pred [B][cap][4] and pred_count [B] int32 are the boxes / kept-count buffers bev_decode_nms_f32 writes, read in
+ * place (only cx, cy of a row are read; a count above cap reads cap rows); gt_xy [N][2] holds the frames' ground-truth
+ * centres back to back, frame b's at rows gt_offset[b] .. gt_offset[b + 1] - 1 (gt_offset [B + 1] int32).  Per
+ * prediction i of a frame, in fp32 with separately rounded products: d_ij = sqrtf(dx dx + dy dy), dx = g_j.x - p_i.x;
+ * (d_i, j_i) = torch.min over j (first minimum; a NaN wins, the first one).  In ascending i: d_i <= thr32 and g_{j_i}
+ * unused -> true positive, the ground truth becomes used and d_i joins the frame's sum; else false positive (no second
+ * try).  thr32: the largest float32 <= the double threshold of the reference's comparison.  counts [B][4] int32 = tp,
+ * fp, fn, status; dist_sum [B] double = the matched d_i added in ascending i.  status 0: the frame is complete; -1:
+ * pred_count[b] < 0, the decode's "finished by the large path" mark -- tp = fp = fn = 0, dist_sum 0; -2 (device entry
+ * only): the frame's offsets decrease or leave [0, N], the same zeros.  Deterministic (integer minima, one addition
+ * order).  workspace: 4-byte aligned, >= bev_detection_match_workspace_bytes(B, N) bytes; that is 0, and the pointer
+ * may be null, while N is at most the kernel's on-chip table (1024 ground truths).  Checked on the host before any
+ * launch: BEV_ERR_ARGS for a negative B, cap or N, a null pred_count / gt_offset / counts / dist_sum, a null pred with
+ * cap > 0, a null gt_xy with N > 0, a workspace that is missing or too small.  B == 0 is a no-op. */
+int64_t bev_detection_match_workspace_bytes(int B, int N);
+int bev_detection_match_f32(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
+                            const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum,
+                            void *workspace, int64_t workspace_bytes, void *stream);
+/* The same scoring on the CPU from host pointers: the literal walk over the predictions with the kernel's per-pair
+ * functions compiled for the host (csrc/bev_metrics.h), no HIP call, no workspace; bit-identical outputs.  The same
+ * argument checks, and BEV_ERR_ARGS for offsets that decrease or leave [0, N]. */
+int bev_detection_match_host(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
+                             const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum);
 int64_t bev_focal_loss_workspace_bytes(int64_t n);
 int bev_focal_loss_fwd_f32(const float *logits, const float *gt, int64_t n, float alpha, float beta, float *loss,
                            float *inv_norm, void *workspace, int64_t workspace_bytes, void *stream);

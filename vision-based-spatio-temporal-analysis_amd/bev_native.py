@@ -66,6 +66,9 @@ SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _i64, _vp]),
     "bev_centernet_targets_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp,
                                         _vp, _vp, _vp, _vp]),
+    "bev_detection_match_workspace_bytes": (_i64, [_i, _i]),
+    "bev_detection_match_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _i64, _vp]),
+    "bev_detection_match_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
     "bev_focal_loss_workspace_bytes": (_i64, [_i64]),
     "bev_focal_loss_fwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "bev_focal_loss_bwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
@@ -1670,17 +1673,33 @@ def maxpool_bwd_nhwc(x: torch.Tensor, dy: torch.Tensor, k: int, stride: int, pad
 # ---------------------------------------------------------------------------
 # decode (detector.py:64-125)
 # ---------------------------------------------------------------------------
+# boxes [B, cap, 4] fp32 and kept [B] int32 as bev_decode_nms_f32 wrote them, the stream they were queued on and the
+# event recorded behind them
+DecodeBuffers = collections.namedtuple("DecodeBuffers", "boxes kept stream ready")
+
+
 class _PendingDecode:
     """A decode whose kernels are queued: the kept / candidate counts travel to pinned host memory behind an
     event, and the host waits for them only when a result is first read (`get`)."""
 
-    def __init__(self, finish):
-        self._finish, self._val = finish, None
+    def __init__(self, finish, raw=None):
+        self._finish, self._val, self._raw = finish, None, raw
 
     def get(self):
         if self._val is None:
             self._val, self._finish = self._finish(), None
         return self._val
+
+    @property
+    def materialised(self) -> bool:
+        """Has the host waited for this decode (get) yet?"""
+        return self._val is not None
+
+    @property
+    def raw(self) -> "DecodeBuffers":
+        """The decode's own output buffers, for consumers that queue behind it instead of waiting (detection_match):
+        read-only.  Until `materialised`, a frame whose kept count is negative awaits the large path."""
+        return self._raw
 
 
 class DetectionList(collections.abc.Sequence):
@@ -1691,6 +1710,10 @@ class DetectionList(collections.abc.Sequence):
 
     def __init__(self, pending: _PendingDecode, which: int):
         self._p, self._w = pending, which
+
+    @property
+    def pending(self) -> _PendingDecode:
+        return self._p
 
     def __getitem__(self, i):
         return self._p.get()[self._w][i]
@@ -1758,7 +1781,7 @@ def decode(heatmap: torch.Tensor, offset: torch.Tensor, size: torch.Tensor, boun
 
     if not lazy:
         return finish()
-    pending = _PendingDecode(finish)
+    pending = _PendingDecode(finish, DecodeBuffers(boxes, nk, queued_on, ready))
     return DetectionList(pending, 0), DetectionList(pending, 1)
 
 
@@ -1917,6 +1940,85 @@ def centernet_targets_host(boxes, frame, B: int, M: int, bev_hw, bounds, res, ov
                                             *_targets_scalars(bounds, res, overlap, min_radius), p(hm), p(indices),
                                             p(mask), p(offset), p(size_log)), "bev_centernet_targets_host")
     return hm, indices, mask, offset, size_log
+
+
+# ---------------------------------------------------------------------------
+# validation scoring (train.py:78-104)
+# ---------------------------------------------------------------------------
+MATCH_STATUS_PENDING = -1  # counts[b, 3]: the frame's decode awaits the large path (kept count < 0)
+MATCH_STATUS_OFFSETS = -2  # counts[b, 3]: the frame's ground-truth offsets decrease or leave [0, N]
+
+
+def match_thr32(match_dist: float) -> float:
+    """The largest float32 <= match_dist: train.py:93 compares min_dist.item(), a double holding the fp32 distance,
+    with the double match_dist; for an fp32 distance d, d <= match_dist exactly when d <= this."""
+    import numpy as np
+    m = float(match_dist)
+    with np.errstate(over="ignore"):
+        t = np.float32(m)
+    if float(t) > m:
+        t = np.nextafter(t, np.float32(-np.inf))
+    return float(t)
+
+
+def detection_match(pred: torch.Tensor, pred_count: torch.Tensor, gt_xy: torch.Tensor, gt_offset: torch.Tensor,
+                    match_dist: float):
+    """The reference's validation matching (train.py:78-104) for a batch in one launch, no synchronisation: pred
+    [B, cap, 4] fp32 and pred_count [B] int32 (the decode's own buffers, read in place), gt_xy [N, 2] fp32 and
+    gt_offset [B + 1] int32 (frame b's ground truths are rows gt_offset[b] .. gt_offset[b + 1] - 1), all on the GPU
+    -> counts [B, 4] int32 (tp, fp, fn, status) and dist_sum [B] float64 (the matched distances added in prediction
+    order) on the GPU.  status: 0 complete, MATCH_STATUS_PENDING, MATCH_STATUS_OFFSETS (include/bev_mi355x.h)."""
+    _require_gpu(pred, gt_xy)
+    _require_gpu(pred_count, gt_offset, dtypes=(torch.int32,), what="int32")
+    if pred.dim() != 3 or pred.shape[2] != 4 or gt_xy.dim() != 2 or gt_xy.shape[1] != 2:
+        raise ValueError(f"detection_match expects pred [B, cap, 4] and gt_xy [N, 2], got {tuple(pred.shape)} "
+                         f"{tuple(gt_xy.shape)}")
+    B, cap, _ = pred.shape
+    N = gt_xy.shape[0]
+    if tuple(pred_count.shape) != (B,) or tuple(gt_offset.shape) != (B + 1,):
+        raise ValueError(f"detection_match expects pred_count [{B}] and gt_offset [{B + 1}], got "
+                         f"{tuple(pred_count.shape)} {tuple(gt_offset.shape)}")
+    if len({t.device for t in (pred, pred_count, gt_xy, gt_offset)}) != 1:
+        raise ValueError("detection_match expects all tensors on one device")
+    pred, pred_count, gt_xy, gt_offset = (t.contiguous() for t in (pred, pred_count, gt_xy, gt_offset))
+    dev = pred.device
+    L = lib()
+    nbytes = int(L.bev_detection_match_workspace_bytes(B, N))
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32) if nbytes else None
+    counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    dist_sum = torch.empty(B, device=dev, dtype=torch.float64)
+    _check(L.bev_detection_match_f32(_ptr(pred), _ptr(pred_count), B, cap, _ptr(gt_xy), _ptr(gt_offset), N,
+                                     match_thr32(match_dist), _ptr(counts), _ptr(dist_sum),
+                                     _ptr(ws) if ws is not None else None, nbytes, _stream(pred)),
+           "bev_detection_match_f32")
+    return counts, dist_sum
+
+
+def detection_match_host(pred, pred_count, gt_xy, gt_offset, match_dist: float):
+    """detection_match on the CPU (bev_detection_match_host: the kernel's per-pair functions compiled for the host; no
+    GPU needed): numpy arrays or CPU tensors -> (counts [B, 4] int32, dist_sum [B] float64) numpy arrays, the same
+    bits as the device entry."""
+    import numpy as np
+    as_np = lambda a, dt: np.ascontiguousarray(a.numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)  # noqa: E731
+    pred, gt_xy = as_np(pred, np.float32), as_np(gt_xy, np.float32)
+    pred_count, gt_offset = as_np(pred_count, np.int32), as_np(gt_offset, np.int32)
+    if pred.ndim != 3 or pred.shape[2] != 4 or gt_xy.ndim != 2 or gt_xy.shape[1] != 2:
+        raise ValueError(f"detection_match_host expects pred [B, cap, 4] and gt_xy [N, 2], got {pred.shape} "
+                         f"{gt_xy.shape}")
+    B, cap, _ = pred.shape
+    N = gt_xy.shape[0]
+    if pred_count.shape != (B,) or gt_offset.shape != (B + 1,):
+        raise ValueError(f"detection_match_host expects pred_count [{B}] and gt_offset [{B + 1}], got "
+                         f"{pred_count.shape} {gt_offset.shape}")
+    counts = np.zeros((B, 4), np.int32)
+    dist_sum = np.zeros(B, np.float64)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)  # noqa: E731
+    rc = lib().bev_detection_match_host(p(pred), p(pred_count), B, cap, p(gt_xy), p(gt_offset), N,
+                                        match_thr32(match_dist), p(counts), p(dist_sum))
+    if rc == BEV_ERR_ARGS:
+        raise ValueError("detection_match_host: gt_offset must start at >= 0, never decrease and end at <= N")
+    _check(rc, "bev_detection_match_host")
+    return counts, dist_sum
 
 
 DECODE_SORT_CHUNK = 8192  # keys per LDS chunk of the large-path sort (bev_decode.hip SORT_CHUNK)
