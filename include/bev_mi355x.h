@@ -961,6 +961,45 @@ int bev_image_jitter_normalize_u8_f32(const uint8_t *src, int N, int H, int W, c
  * checking the arithmetic without a GPU, and for another host to check its own port against. */
 int bev_image_jitter_u8_host(const uint8_t *src, int N, int H, int W, const int32_t *params, uint8_t *out_u8);
 
+/* Adam / AdamW parameter update (train.py:46-52 optim.Adam / optim.AdamW, stepped at train.py:238-255) for all T
+ * tensors of a parameter group in one launch, aware of GradScaler's device scalars.  Added under ABI 18 (new entries
+ * only; the number does not move).  The arithmetic is a defined fp32 sequence (csrc/bev_optim.h: torch's
+ * _single_tensor_adam op for op with every fused multiply-add split into two roundings), shared by the kernel and
+ * the host entry, which therefore agree bit for bit.
+ *
+ * The table is T records of eight 64-bit words, 8-B aligned:
+ *   words 0-3  p, g, m (exp_avg), v (exp_avg_sq): n fp32 each, dense and in one element order, 4-B aligned (16-byte
+ *              loads and stores are used for a tensor when all four are 16-B aligned); g is only read
+ *   word 4     step_in:  one fp32, the number of updates so far (what torch keeps as state["step"])
+ *   word 5     step_out: one fp32 in ANOTHER buffer: step_in + 1, or step_in when found_inf is set.  The caller swaps
+ *              the two after the call.  No part of a launch reads a counter that the launch writes.
+ *   word 6     n, the element count (>= 0)
+ *   word 7     the tensor's first chunk: 0 for record 0, the previous record's first chunk plus
+ *              max(1, ceil(n / bev_adam_chunk_elems())) of the previous record after it
+ * The sum of those chunk counts over the table is total_chunks, the launch's grid.
+ *
+ * lr, betas, eps, weight_decay: host scalars, as Python doubles; decoupled != 0: AdamW's decay (p *= 1 - lr * wd),
+ * else Adam's (g += wd * p); weight_decay == 0: none.  grad_scale (the gradients are multiplied by
+ * float(1 / double(*grad_scale)) as they are read; never modified in memory) and found_inf (*found_inf != 0: nothing
+ * is written but step_out = step_in) are single fp32 values and may be NULL.
+ *
+ * host: bytes of a table of T records. */
+int64_t bev_adam_table_bytes(int T);
+/* host: elements per chunk (one workgroup each). */
+int bev_adam_chunk_elems(void);
+/* device: table, grad_scale, found_inf and everything the table points at in device memory.  Allocates nothing and
+ * synchronises nothing.  Arguments are checked on the host before the launch: BEV_ERR_ARGS for a null or misaligned
+ * table, T < 0, a beta outside [0, 1), total_chunks < T or above 2^31 - 1; T == 0 is a no-op.  A chunk index that the
+ * table does not cover is ignored by the kernel.  Element offsets are 64-bit. */
+int bev_adam_step_f32(const void *table_dev, int T, int64_t total_chunks, double lr, double beta1, double beta2,
+                      double eps, double weight_decay, int decoupled, const float *grad_scale_dev,
+                      const float *found_inf_dev, void *stream);
+/* host, no HIP call: the same per-element function on host memory (table, scalars and tensors; word 7 is not read).
+ * For checking the arithmetic without a GPU, and as the CPU path of bev_optim.Adam.  The same argument checks, and
+ * BEV_ERR_ARGS for a record with n < 0 or a null pointer. */
+int bev_adam_step_host(const void *table_host, int T, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, int decoupled, const float *grad_scale, const float *found_inf);
+
 /* BEVNet head operand (model_wrapper.py:69-75 -- proj bias add, pos-enc concat; the reference's torch.cat of the
  * projection [B,P,Hb,Wb] and pos_enc [2,Hb,Wb]): x [B][Hb][Wb][cp] channels-last = (s + bias, pos, 0...) per cell, s the
  * fused warp-sum of the projected views [B][P][Hb][Wb]; cp >= P + 2 (the head's padded input width), P <= 512.  The

@@ -1,6 +1,7 @@
 """Training-step timing (BASELINE config 3 shape, one GPU): ResNet-50 trunk + proj -> IPM warp -> head.
 
     python tools/train_step_bench.py [--steps 5] [--bevnet] [--amp] [--fp32-kernels] [--torch-targets | --ab-targets R]
+                                        [--native-adam | --ab-adam R]
 
 Default: the hot path alone -- CNNEncoder (trunk trainable, native forward + backward) -> fused warp
 + mean (native forward + backward) -> sum(out * r) -> Adam step.  --bevnet: the full BEVNet (encoder,
@@ -40,6 +41,10 @@ def main():
                     "(model_wrapper.NATIVE_TARGETS off)")
     ap.add_argument("--ab-targets", type=int, default=0, metavar="ROUNDS", help="A/B in one process: ROUNDS times a "
                     "native-targets run then a torch-targets run of --steps steps each, one JSON line per run")
+    ap.add_argument("--native-adam", action="store_true", help="bev_optim.Adam (one launch per step, no GradScaler "
+                    "host wait) in place of torch.optim.Adam")
+    ap.add_argument("--ab-adam", type=int, default=0, metavar="ROUNDS", help="A/B in one process: ROUNDS times a "
+                    "torch.optim.Adam run then a bev_optim.Adam run of --steps steps each, one JSON line per run")
     ap.add_argument("--eager-decode", action="store_true", help="A/B: BEVNet.forward synchronises on its decode")
     ap.add_argument("--loss-graph", action="store_true", help="A/B: BEVNet.loss as a replayed graph pair "
                     "(model_wrapper.LOSS_GRAPHS)")
@@ -49,6 +54,7 @@ def main():
                     "re-scans it for the argmax instead of taking the forward's argmax bytes (trunk_grad.MAXPOOL_ARG)")
     a = ap.parse_args()
     import bev_native
+    import bev_optim
     bev_native.AMP_HALF_CONVS = not a.fp32_kernels
     if a.no_mask_bytes:
         from models.encoders import trunk_grad
@@ -65,6 +71,7 @@ def main():
         name, v = kv.split("=")
         bev_native.tune(getattr(bev_native, "TUNE_" + name.upper()), int(v))
     scaler = torch.amp.GradScaler("cuda") if a.amp else None
+    arm = {"adam": "native" if a.native_adam else "torch"}  # which optimizer step() uses (each keeps its own state)
     dev = torch.device("cuda:0")
     V, H, W = 7, 1080, 1920
     K, Rt = bev_rig.rig(V, H, W, 1)
@@ -84,9 +91,11 @@ def main():
         with torch.no_grad():
             model.eval()(batch)
         model.train()
-        opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+        opts = {"torch": torch.optim.Adam(model.parameters(), lr=1e-4),
+                "native": bev_optim.Adam(model.parameters(), lr=1e-4)}
 
         def step():
+            opt = opts[arm["adam"]]
             opt.zero_grad(set_to_none=True)
             with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
                 loss = model.loss(model(batch), targets, {})["total_loss"]
@@ -106,10 +115,12 @@ def main():
         with torch.no_grad():
             enc.eval()(images)
         enc.train()
-        opt = torch.optim.Adam(enc.parameters(), lr=1e-4)
+        opts = {"torch": torch.optim.Adam(enc.parameters(), lr=1e-4),
+                "native": bev_optim.Adam(enc.parameters(), lr=1e-4)}
         r = torch.randn(1, 64, 480, 1440, device=dev)
 
         def step():
+            opt = opts[arm["adam"]]
             opt.zero_grad(set_to_none=True)
             with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
                 out = geom.forward_fused(enc(images), Kd, Rtd, (H, W), "mean")
@@ -125,8 +136,9 @@ def main():
     for _ in range(a.warmup):
         step()
 
-    def run(native_targets: bool):
+    def run(native_targets: bool, adam: str = arm["adam"]):
         _mw.NATIVE_TARGETS = native_targets
+        arm["adam"] = adam
         step()  # the arm's own first step (workspace, allocator) stays out of the timing
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -134,6 +146,7 @@ def main():
             loss = step()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
+        updated = [p for g in opts[adam].param_groups for p in g["params"] if p.grad is not None]
         print(json.dumps({"what": "bevnet train step" if a.bevnet else "hot-path train step", "backbone": a.backbone,
                           "tune": a.tune, "bev": [480, 1440], "cameras": V, "img": [H, W], "feat_dim": 64,
                           "bev_proj_ch": a.proj_ch if a.bevnet else None,
@@ -141,11 +154,16 @@ def main():
                           "decode": "eager" if a.eager_decode else "lazy",
                           "loss_impl": "torch" if a.torch_loss else "native",
                           "targets_impl": "native" if native_targets else "torch",
-                          "targets": "device" if a.device_targets else "host",
+                          "targets": "device" if a.device_targets else "host", "adam_impl": adam,
+                          "adam_tensors": len(updated), "adam_elems": sum(p.numel() for p in updated),
                           "ms_per_step": round(dt * 1e3, 2), "frames_per_s": round(1.0 / dt, 3),
                           "loss": float(loss)}), flush=True)
 
-    if a.ab_targets:
+    if a.ab_adam:
+        for _ in range(a.ab_adam):
+            run(not a.torch_targets, "torch")
+            run(not a.torch_targets, "native")
+    elif a.ab_targets:
         for _ in range(a.ab_targets):
             run(True)
             run(False)

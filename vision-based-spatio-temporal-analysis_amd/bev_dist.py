@@ -185,24 +185,38 @@ def ddp_wrap(model: torch.nn.Module, device: Optional[torch.device] = None, buck
                                    bucket_cap_mb=bucket_cap_mb, gradient_as_bucket_view=True)
 
 
-def train_step(model, batch, targets, optimizer, loss_cfg=None, scaler=None) -> dict:
+def train_step(model, batch, targets, optimizer, loss_cfg=None, scaler=None, accum_steps: int = 1,
+               micro_step: int = 0) -> dict:
     """One optimisation step as train.py:238-255: forward, BEVNet.loss, backward (DDP all-reduces the
     gradients when `model` is wrapped), optimizer step.  With a `torch.amp.GradScaler` (the reference's
     default, RUNTIME.USE_AMP: true) the forward and loss run under autocast(float16) -- the native kernels
     compute in fp32 inside it (bev_native.amp_fwd) -- and the step goes through scaler.scale / step / update,
-    which skips it when a gradient is not finite.  Returns the losses."""
-    optimizer.zero_grad(set_to_none=True)
+    which skips it when a gradient is not finite.  Returns the losses.
+
+    Gradient accumulation (TRAIN.ACCUM_STEPS, train.py:242-255): `micro_step` counts the calls; the loss that is
+    differentiated is divided by `accum_steps`, the gradients are cleared only when micro_step % accum_steps == 0
+    and the optimizer steps only when (micro_step + 1) % accum_steps == 0.  The returned losses are undivided.
+    Under DDP every micro-step all-reduces (no no_sync()): the same sum, more traffic."""
+    if accum_steps < 1:
+        raise ValueError(f"accum_steps must be >= 1, got {accum_steps}")
+    if micro_step % accum_steps == 0:
+        optimizer.zero_grad(set_to_none=True)
+    do_step = (micro_step + 1) % accum_steps == 0
     core = getattr(model, "module", model)
     if scaler is not None:
         with torch.autocast("cuda", dtype=torch.float16):
             preds = model(batch)
             losses = core.loss(preds, targets, loss_cfg or {})
-        scaler.scale(losses["total_loss"]).backward()
-        scaler.step(optimizer)
-        scaler.update()
+        total = losses["total_loss"] if accum_steps == 1 else losses["total_loss"] / accum_steps
+        scaler.scale(total).backward()
+        if do_step:
+            scaler.step(optimizer)
+            scaler.update()
     else:
         preds = model(batch)
         losses = core.loss(preds, targets, loss_cfg or {})
-        losses["total_loss"].backward()
-        optimizer.step()
+        total = losses["total_loss"] if accum_steps == 1 else losses["total_loss"] / accum_steps
+        total.backward()
+        if do_step:
+            optimizer.step()
     return {k: float(v.detach()) for k, v in losses.items()}

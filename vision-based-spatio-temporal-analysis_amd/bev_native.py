@@ -180,6 +180,10 @@ SIGNATURES = {
     "bev_conv2d_chain_x6_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i,
                                      _vp, _i, _i, _vp]),
     "bev_conv2d_dual_x6_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "bev_adam_table_bytes": (_i64, [_i]),
+    "bev_adam_chunk_elems": (_i, []),
+    "bev_adam_step_f32": (_i, [_vp, _i, _i64, _d, _d, _d, _d, _d, _i, _vp, _vp, _vp]),
+    "bev_adam_step_host": (_i, [_vp, _i, _d, _d, _d, _d, _d, _i, _vp, _vp]),
 }
 
 
@@ -2019,6 +2023,66 @@ def detection_match_host(pred, pred_count, gt_xy, gt_offset, match_dist: float):
         raise ValueError("detection_match_host: gt_offset must start at >= 0, never decrease and end at <= N")
     _check(rc, "bev_detection_match_host")
     return counts, dist_sum
+
+
+# ---------------------------------------------------------------------------
+# Adam / AdamW parameter update (train.py:46-52, 238-255)
+# ---------------------------------------------------------------------------
+ADAM_REC_WORDS = 8  # include/bev_mi355x.h: p, g, m, v, step_in, step_out, n, first chunk
+
+
+def adam_chunk_elems() -> int:
+    return int(lib().bev_adam_chunk_elems())
+
+
+def adam_table(records) -> "tuple":
+    """The table of bev_adam_step_f32 / bev_adam_step_host for `records`, a sequence of (p, g, m, v, step_in,
+    step_out, n) with the first six as addresses: (int64 numpy array [T, 8], total chunks)."""
+    import numpy as np
+    C = adam_chunk_elems()
+    tab = np.zeros((len(records), ADAM_REC_WORDS), np.int64)
+    chunk = 0
+    for t, rec in enumerate(records):
+        tab[t, :7] = rec
+        tab[t, 7] = chunk
+        chunk += max(1, -(-int(rec[6]) // C))
+    assert tab.nbytes == int(lib().bev_adam_table_bytes(len(records)))
+    return tab, chunk
+
+
+def adam_step(table_dev: torch.Tensor, T: int, total_chunks: int, lr: float, beta1: float, beta2: float, eps: float,
+              weight_decay: float, decoupled: bool, grad_scale: torch.Tensor = None, found_inf: torch.Tensor = None):
+    """One launch of the Adam / AdamW update over the T tensors of table_dev (adam_table's array on the device,
+    int64): p, m, v and the step_out counters are written, unless *found_inf != 0.  grad_scale / found_inf: fp32
+    device scalars (GradScaler's) or None.  No allocation, no synchronisation."""
+    _require_gpu(table_dev, dtypes=(torch.int64,), what="int64")
+    _require_gpu(grad_scale, found_inf)
+    for t in (grad_scale, found_inf):
+        if t is not None and (t.numel() != 1 or t.device != table_dev.device):
+            raise ValueError("adam_step: grad_scale / found_inf are single fp32 values on the table's device")
+    if table_dev.numel() < T * ADAM_REC_WORDS or not table_dev.is_contiguous():
+        raise ValueError(f"adam_step: the table holds {table_dev.numel()} words, {T} records need {T * ADAM_REC_WORDS}")
+    _check(lib().bev_adam_step_f32(_ptr(table_dev), T, total_chunks, lr, beta1, beta2, eps, weight_decay,
+                                   int(bool(decoupled)), _ptr(grad_scale), _ptr(found_inf), _stream(table_dev)),
+           "bev_adam_step_f32")
+
+
+def adam_step_host(table, T: int, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                   decoupled: bool, grad_scale=None, found_inf=None):
+    """adam_step on the CPU (bev_adam_step_host: the kernel's per-element function compiled for the host; no GPU
+    needed).  table: adam_table's array over host addresses; grad_scale / found_inf: a float (or anything float()
+    takes) or None."""
+    import numpy as np
+    table = np.ascontiguousarray(table, dtype=np.int64)
+    if table.size < T * ADAM_REC_WORDS:
+        raise ValueError(f"adam_step_host: the table holds {table.size} words, {T} records need {T * ADAM_REC_WORDS}")
+    gs = None if grad_scale is None else ctypes.c_float(float(grad_scale))
+    fi = None if found_inf is None else ctypes.c_float(float(found_inf))
+    rc = lib().bev_adam_step_host(ctypes.c_void_p(table.ctypes.data if table.size else None), T, lr, beta1, beta2, eps,
+                                  weight_decay, int(bool(decoupled)),
+                                  ctypes.cast(ctypes.pointer(gs), _vp) if gs is not None else None,
+                                  ctypes.cast(ctypes.pointer(fi), _vp) if fi is not None else None)
+    _check(rc, "bev_adam_step_host")
 
 
 DECODE_SORT_CHUNK = 8192  # keys per LDS chunk of the large-path sort (bev_decode.hip SORT_CHUNK)
