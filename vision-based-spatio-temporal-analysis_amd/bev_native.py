@@ -461,6 +461,17 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def mark_written(*tensors) -> None:
+    """Tell torch that native code wrote these tensors (None entries skipped): advances each one's version counter,
+    as a torch in-place op would.  The kernels write through raw pointers, which torch cannot see; every cache of
+    operands derived from a parameter or buffer (packed panels, BN-folded weights, fp16 copies) is keyed on
+    (data_ptr, _version), and autograd's saved-tensor check reads the same counter.  Host only: no launch, no
+    synchronisation, nothing read back; it works on leaf parameters and inside no_grad."""
+    ts = [t for t in tensors if t is not None]
+    if ts:
+        torch.autograd.graph.increment_version(ts)
+
+
 def _out_hw(H, W, KH, KW, stride, pad, dilation=1):  # the expression the C entry points check Ho, Wo against
     return tuple((n + 2 * pad - dilation * (k - 1) - 1) // stride + 1 for n, k in ((H, KH), (W, KW)))
 
@@ -1235,6 +1246,7 @@ def batchnorm_finalize_tiles(tiles: torch.Tensor, M: int, gamma, beta, running_m
                                                     _ptr(running_var), _ptr(mean), _ptr(rstd), _ptr(scale),
                                                     _ptr(shift), _stream(tiles))
     _check(rc, "bev_batchnorm_finalize_tiles_f32")
+    mark_written(running_mean, running_var)
     return mean, rstd, scale, shift
 
 
@@ -1440,6 +1452,7 @@ def channel_scale_(y: torch.Tensor, gate: torch.Tensor) -> torch.Tensor:
     P = y.numel() // (N * C)
     rc = lib().bev_channel_scale_f32(_ptr(y), N, P, C, _ptr(gate), _stream(y))
     _check(rc, "bev_channel_scale_f32")
+    mark_written(y)
     return y
 
 
@@ -2054,7 +2067,9 @@ def adam_step(table_dev: torch.Tensor, T: int, total_chunks: int, lr: float, bet
               weight_decay: float, decoupled: bool, grad_scale: torch.Tensor = None, found_inf: torch.Tensor = None):
     """One launch of the Adam / AdamW update over the T tensors of table_dev (adam_table's array on the device,
     int64): p, m, v and the step_out counters are written, unless *found_inf != 0.  grad_scale / found_inf: fp32
-    device scalars (GradScaler's) or None.  No allocation, no synchronisation."""
+    device scalars (GradScaler's) or None.  No allocation, no synchronisation.
+    The table holds addresses, not tensors: the caller marks what the launch writes (mark_written on every p, m
+    and v of the table, as bev_optim.Adam.step does), or caches keyed on the parameters' versions go stale."""
     _require_gpu(table_dev, dtypes=(torch.int64,), what="int64")
     _require_gpu(grad_scale, found_inf)
     for t in (grad_scale, found_inf):
@@ -2071,7 +2086,7 @@ def adam_step_host(table, T: int, lr: float, beta1: float, beta2: float, eps: fl
                    decoupled: bool, grad_scale=None, found_inf=None):
     """adam_step on the CPU (bev_adam_step_host: the kernel's per-element function compiled for the host; no GPU
     needed).  table: adam_table's array over host addresses; grad_scale / found_inf: a float (or anything float()
-    takes) or None."""
+    takes) or None.  As with adam_step, marking the written tensors (mark_written) is the caller's."""
     import numpy as np
     table = np.ascontiguousarray(table, dtype=np.int64)
     if table.size < T * ADAM_REC_WORDS:
@@ -2217,6 +2232,7 @@ def batchnorm_train_fwd(z: torch.Tensor, gamma, beta, running_mean, running_var,
                                                _ptr(running_mean), _ptr(running_var), _ptr(mean), _ptr(rstd), _ptr(scale),
                                                _ptr(shift), _ptr(ws), _stream(z))
     _check(rc, "bev_batchnorm_train_fwd_f32")
+    mark_written(running_mean, running_var)
     return mean, rstd, scale, shift
 
 

@@ -11,6 +11,9 @@
 * State and param_groups have torch.optim.Adam's keys and types (`step` an fp32 0-dim tensor, `exp_avg`,
   `exp_avg_sq`), so state dicts load both ways; `lr` is read from the group at every step, so torch's schedulers work.
 * CPU parameters take bev_adam_step_host, the same arithmetic compiled for the host.
+* Every step advances the version counter of each updated parameter, `exp_avg` and `exp_avg_sq`
+  (bev_native.mark_written), as torch.optim.Adam's in-place ops do: the models' packed-weight caches, keyed on
+  (data_ptr, _version), re-pack at their next forward.  Host bookkeeping only: no launch, no read-back.
 
 The arithmetic is a defined fp32 sequence (csrc/bev_optim.h): torch's single-tensor Adam op for op with every fused
 multiply-add split in two.  Not offered: amsgrad, maximize, capturable / differentiable, tensor learning rates,
@@ -153,6 +156,10 @@ class Adam(torch.optim.Optimizer):
                 else:
                     table, _ = _nat.adam_table(records)
                     _nat.adam_step_host(table, len(records), *hyper, grad_scale=grad_scale, found_inf=found_inf)
+                # the update went through raw pointers: advance the version counters as torch's in-place ops would,
+                # so operands cached under (data_ptr, _version) are rebuilt.  Unconditional -- found_inf lives on the
+                # device and is not read here; a skipped step costs one needless re-pack
+                _nat.mark_written(*[t for p, _, m, v, _, _ in ops for t in (p, m, v)])
                 for p, _, _, _, s_in, s_out in ops:  # the swap: what the launch wrote is the parameter's step now
                     self.state[p]["step"] = s_out
                     self._spare[p] = s_in

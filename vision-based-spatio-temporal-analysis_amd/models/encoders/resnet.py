@@ -89,8 +89,13 @@ SPLIT_CHAIN = True
 class FoldedConv:
     """conv (+ eval-mode BN) folded into a packed MFMA weight panel + bias, cached on device.
 
-    The cache is keyed on the parameters' storage and version counters, so an
-    optimizer step or load_state_dict triggers a re-pack on the next call.
+    The cache is keyed on (data_ptr, _version) of the conv's and the BN's parameters and running statistics, so
+    whatever advances a version counter triggers a re-pack on the next call: torch's in-place ops (torch.optim,
+    load_state_dict, mul_ ...) do it themselves, and the native writers, which go through raw pointers, do it by
+    bev_native.mark_written -- bev_optim's Adam / AdamW step and the train-mode BatchNorm's running-statistics
+    update (batchnorm_train_fwd / batchnorm_finalize_tiles).  A native writer that skips the call leaves every
+    panel stale (tests/test_weight_cache_gpu.py); a new tensor at a recycled address with an equal counter is not
+    told apart (open).
     With `split_ok` (the ResNet trunk and the encoder proj) an NHWC conv with Ci % 16 == 0 runs in the
     arithmetic bev_native.conv_arith() selects: "bf16x6" packs the split-bf16 panel (bev_conv2d_x6_f32), "f32"
     the exact-f32 MFMA panel (bev_conv2d_f32).  The chained bottleneck kernels exist in both and take the panel of
