@@ -103,7 +103,11 @@ const char *bev_build_source_hash(void);
  * BEV_TUNE_WARP_TILE_BAND: fused warp (per-tile kernel) tile order inside each XCD's contiguous range: 1 = row-major
  *   tiles, n (2..64) = bands of n tile rows walked column by column, so vertically neighbouring tiles (which share
  *   source pixels) are resident together and share that XCD's L2; 0 (default) = bands of 4 for >= 12 views,
- *   row-major otherwise (measured: 16-camera 4K rig -3.7 %, 7-camera rig +2.2 % with bands of 4).  Same results. */
+ *   row-major otherwise (measured: 16-camera 4K rig -3.7 %, 7-camera rig +2.2 % with bands of 4).  Same results.
+ * BEV_TUNE_CONV_X6_STRIP: chained bottleneck bodies (bev_conv2d_chain_x6_f32 / _dual_) with a pre-split operand, a
+ *   3x3 / stride 1 / pad 1 conv2 over 64 channels and a 64-channel h2 (ResNet layer1): 1 (default) = conv2's operand
+ *   staged once per tap row (a strip of 130 pixels serves the three taps of a row), 0 = once per tap.  Same results
+ *   bit for bit. */
 #define BEV_TUNE_CONV_TILE 1
 #define BEV_TUNE_WARP_POOL_KB 2
 #define BEV_TUNE_WARP_KERNEL 3
@@ -123,6 +127,7 @@ const char *bev_build_source_hash(void);
 #define BEV_TUNE_WARP_SPAN 19
 #define BEV_TUNE_WARP_TILE_BAND 20
 #define BEV_TUNE_CONV_H16_BUF 21
+#define BEV_TUNE_CONV_X6_STRIP 22
 int bev_tune(int knob, int value);
 
 /* ---------------------------------------------------------------------------

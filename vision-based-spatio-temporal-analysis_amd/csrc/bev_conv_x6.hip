@@ -847,7 +847,125 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
 // are 1-KiB runs, one DMA instruction each, read back as conflict-free ds_read_b128 (lane l at 16 l) -- so every
 // vector-memory operation of the loop is a DMA issued one K step ahead and waited for at the step's end.  (With B
 // in registers hipcc re-issued the fragment loads next to their MFMAs and waited on each: L2 latency per slice.)
-template <int WM, int WN, int TM, int TN, int CHAIN = 0>
+//
+// STRIP (the layer1 chains: 3x3 / stride 1 / pad 1 / Ci = 64, 128 x 64 tile; BEV_TUNE_CONV_X6_STRIP): the taps
+// kx = 0, 1, 2 of one ky read the same h1 pixels shifted by one, and a tile is 128 consecutive pixels in (n, oy, ox)
+// order -- so a STRIP of 130 consecutive pixels per ky serves all three kx, staged once instead of three times
+// (A bytes L2 -> LDS per workgroup 432 KiB -> 162 KiB; with B's 216 KiB the mainloop moves 0.58x the bytes).
+// LDS: two half-strips (channels 0..31, 32..63) of 3 planes x 144 rows x 64 B (130 rows used: 9 DMA groups of 16),
+// the chunk swizzle above -- conflict-free for 16 consecutive rows from ANY start row, so the shifted fragment reads
+// stay conflict-free -- then the two B stages: 55,296 + 24,576 = 79,872 B (two workgroups per CU).
+// Strip row sr of tap row ky holds pixel q = p + (ky - 1) W, p = m0 - 1 + sr; zero when p is outside [0, M) or
+// y_p + ky - 1 outside [0, H): the tap above / below the image or in another image.  A horizontal edge cannot be
+// zeroed there (a pixel valid for one output is out of bounds for its neighbour): the lane whose output has ox == 0
+// (ox == W - 1) takes a zero A fragment in the kx = 0 (kx = 2) slices, by a select, so a NaN / Inf in the
+// neighbouring row's pixel does not leak.  K steps in today's order (ky, kx, channel half): output row R reads strip
+// row R + kx of the step's half.  Half-strip 0 of ky + 1 is issued in step (ky, 2, half 1) -- its last reader was
+// the step before -- and half-strip 1 of ky in step (ky, 0, half 0); each is waited for at the end of the step that
+// issues it, B stays one step ahead: no further buffers, no bubble.  Same slices, same x6_dot: bit-identical.
+__device__ __forceinline__ void x6s_strip_mainloop(const ConvX &a, unsigned char *lds_raw, f32x16 (&acc)[1][2],
+                                                   int wave, int lane, int64_t m0) {
+    constexpr int SROWS = 144, SUSED = 130;  // strip rows staged / read (rows 0 .. 127 + 2)
+    constexpr int SPL = SROWS * 32;          // bf16 per strip plane
+    constexpr int HSB = 3 * SPL * 2;         // bytes per half-strip
+    constexpr int BSTB = 2 * 6 * 1024;       // bytes per B stage: [cb 2][slice 2][plane 3] fragment runs of 1 KiB
+    constexpr int NPC = 27;                  // DMA pieces (plane, 16-row group) per half-strip
+    constexpr int NP = (NPC + 3) / 4;        // ... per wave: piece q = wave + 4 i
+    constexpr int YOUT = -(1 << 30);         // "row" of a strip pixel that is never inside the image
+    const __bf16 *lds = (const __bf16 *)lds_raw;
+    const unsigned lbase = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr(lds_raw));
+    const int r32 = lane & 31, h = lane >> 5;
+
+    // DMA: lane l of a piece copies strip row 16 g + (l >> 2), physical chunk l & 3 = logical chunk
+    // (l & 3) ^ ((row >> 2) & 3) (16 g >> 2 is a multiple of 4: the same for every group)
+    const int lc = (lane & 3) ^ ((lane >> 4) & 3);
+    const int64_t loff = (m0 - 1 + (lane >> 2)) * 64 + 8 * lc;  // lane part of the source offset (bf16)
+    int yv[NP];  // image row of this lane's strip pixel in piece i, YOUT outside [0, M) and for rows never read
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int g = (wave + 4 * i) % 9;
+        const int sr = 16 * g + (lane >> 2);
+        const int64_t p = m0 - 1 + sr;
+        const bool ok = sr < SUSED && p >= 0 && p < a.M;
+        yv[i] = ok ? (int)((p / a.W) % a.H) : YOUT;
+    }
+    auto issue_strip = [&](int half, int ky) {
+        const int64_t so = (int64_t)(ky - 1) * a.W * 64 + half * 32;
+        const unsigned d0 = lbase + (unsigned)(half * HSB);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int q = wave + 4 * i;  // wave-uniform
+            if (q < NPC) {
+                const int pl = q / 9, g = q % 9;
+                const bool in = (unsigned)(yv[i] + ky - 1) < (unsigned)a.H;
+                const __bf16 *src = a.xs + (loff + so + (int64_t)g * (16 * 64) + pl * a.xps);
+                lds_dma16(in ? (const void *)src : (const void *)g_xzero4, d0 + (unsigned)(pl * SPL * 2 + g * 1024));
+            }
+        }
+    };
+    const int S = a.Kp / XBK;  // 16-deep slices (36)
+    const __bf16 *bsrc = a.wp + lane * 8;
+    int kstep = 0;
+    auto issue_b = [&](int buf) {  // piece q = (cb, slice, plane) of K step kstep: panel run ((cb S + 2 ks + sl) 3 + p)
+        const unsigned db = lbase + (unsigned)(2 * HSB + buf * BSTB);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int q = wave + 4 * i, cbl = q / 6, r = q % 6;
+            lds_dma16(bsrc + ((int64_t)cbl * S + 2 * kstep + r / 3) * 1536 + (r % 3) * 512, db + (unsigned)(q * 1024));
+        }
+        ++kstep;
+    };
+
+    // this lane's output row (A fragment row r32 of the wave's band) and its horizontal edges
+    const int R = wave * 32 + r32;
+    const int ox = (int)((m0 + R) % a.W);
+    const bool e0 = ox == 0, e2 = ox == a.W - 1;
+    const bool any0 = __builtin_amdgcn_ballot_w64(e0) != 0, any2 = __builtin_amdgcn_ballot_w64(e2) != 0;
+
+    issue_b(0);
+    issue_strip(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {  // K step (ky, kx, half)
+            const int kx = t >> 1, half = t & 1;
+            if (t < 5 || ky < 2) issue_b((t + 1) & 1);
+            if (t == 0) issue_strip(1, ky);
+            if (t == 5 && ky < 2) issue_strip(0, ky + 1);
+            const __bf16 *As = lds + half * (3 * SPL);
+            const __bf16 *Bs = (const __bf16 *)(lds_raw + 2 * HSB + (t & 1) * BSTB) + lane * 8;
+            const int r = R + kx;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                bf16x8 fb[2][3], fa[3];
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) fb[j][p] = *(const bf16x8 *)(Bs + ((j * 2 + kk) * 3 + p) * 512);
+                const int ph = (2 * kk + h) ^ ((r >> 2) & 3);
+#pragma unroll
+                for (int p = 0; p < 3; ++p) fa[p] = *(const bf16x8 *)(As + p * SPL + r * 32 + ph * 8);
+                if ((kx == 0 && any0) || (kx == 2 && any2)) {  // wave-uniform: most waves hold no edge pixel
+                    const bool z = kx == 0 ? e0 : e2;
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+                        u32x4 v = __builtin_bit_cast(u32x4, fa[p]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = z ? 0u : v[e];
+                        fa[p] = __builtin_bit_cast(bf16x8, v);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) x6_dot(acc[0][j], fa, fb[j]);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMAs of the next step landed
+            __syncthreads();                                   // everyone's; this step's buffers are free again
+        }
+    }
+}
+
+template <int WM, int WN, int TM, int TN, int CHAIN = 0, bool STRIP = false>
 __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
     constexpr bool BLDS = CHAIN > 0;
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -858,9 +976,11 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
     constexpr int RG = RW / 16;      // 16-row DMA groups per wave and plane
     constexpr int BPW = BLDS ? BN / 32 * 6 / 4 : 0;  // B pieces (1 KiB) per wave and K step
     constexpr int EPIB = CHAIN ? x6_chain_lds_bytes<BM, BN>() : x6_epi_bytes<TN>();
-    constexpr int LDSB = (2 * STAGE * 2 > EPIB) ? 2 * STAGE * 2 : EPIB;
+    constexpr int MAINB = STRIP ? 2 * (3 * 144 * 64) + 2 * BST * 2 : 2 * STAGE * 2;  // STRIP: half-strips + B stages
+    constexpr int LDSB = (MAINB > EPIB) ? MAINB : EPIB;
     static_assert(RW % 16 == 0, "whole DMA groups per wave");
     static_assert(!BLDS || (BN / 32 * 6) % 4 == 0, "whole B pieces per wave");
+    static_assert(!STRIP || (CHAIN > 0 && WM == 4 && WN == 1 && TM == 1 && TN == 2), "strip: the 128 x 64 chains");
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDSB];
     const __bf16 *lds = (const __bf16 *)lds_raw;
 
@@ -871,6 +991,13 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
     const unsigned bid = xcd_block(blockIdx.x, gridDim.x);  // the n_tiles blocks of the same A rows on one XCD
     const int64_t m0 = (int64_t)(bid / n_tiles) * BM;
     const int n0 = (bid % n_tiles) * BN;
+
+    if constexpr (STRIP) {  // Ci = Co = 64, 3x3 / 1 / 1 (conv_x6() checks): one column tile, n0 = 0
+        f32x16 sacc[1][2] = {{(f32x16){0}, (f32x16){0}}};
+        x6s_strip_mainloop(a, lds_raw, sacc, wave, lane, m0);
+        x6_chain_epilogue<WM, WN, TM, TN, CHAIN == 2 ? 4 : 0>(a, lds_raw, sacc, wave, lane, wm, wn, m0);
+        return;
+    }
 
     // DMA rows of this lane: wave * RW + 16 g + (lane >> 2); physical chunk lane & 3 holds logical chunk
     // (lane & 3) ^ ((row >> 2) & 3)
@@ -1022,6 +1149,7 @@ __global__ void k_split3(const float *__restrict__ x, int64_t n, __bf16 *__restr
 int g_x6_tile = 0;  // 0 automatic, 1 = 128 x 128, 2 = 128 x 64
 int g_x6_nt = 0;    // BEV_TUNE_CONV_X6_NT: 1 = non-temporal activation loads in the 32-deep kernels
 int g_x6_kernel = 0;  // 0 automatic (k_conv_x6b wherever it applies), 1 = k_conv_x6 (16-deep K steps) everywhere
+int g_x6_strip = 1;   // BEV_TUNE_CONV_X6_STRIP: 1 = the strip-staged mainloop in the layer1 chains, 0 = one staging per tap
 
 // one workgroup per BM x BN output tile; `kernel` = the k_conv_x6 / k_conv_x6b / k_conv_x6s instance with that tile
 // (BM = WM TM 32, BN = WN TN 32)
@@ -1099,8 +1227,13 @@ int conv_x6(const X6Call &c, hipStream_t st) {
 
     // The chains.  A pre-split operand (conv1 handed over its output split) is staged by LDS-DMA (k_conv_x6s), same K
     // order.  h2 of 128 channels: the 64 x 128 tile (h2 planes 52 KiB of LDS).
+    // The layer1 shape of a pre-split operand (3x3 / 1 / 1 over 64 channels, 128 x 64 tile): one strip per tap row.
+    const bool strip = g_x6_strip && c.xs && c.KH == 3 && c.KW == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 &&
+                       c.Ci == 64;
+    if (c.form == X6_CHAIN_DUAL && strip) return launch_x6(k_conv_x6s<4, 1, 1, 2, 2, true>, 128, 64, a, st);
     if (c.form == X6_CHAIN_DUAL)
         return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 2> : k_conv_x6b<4, 1, 1, 2, false, 2>, 128, 64, a, st);
+    if (c.form == X6_CHAIN && c.Co == 64 && strip) return launch_x6(k_conv_x6s<4, 1, 1, 2, 1, true>, 128, 64, a, st);
     if (c.form == X6_CHAIN && c.Co == 64)
         return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 1> : k_conv_x6b<4, 1, 1, 2, false, 1>, 128, 64, a, st);
     if (c.form == X6_CHAIN)
@@ -1522,6 +1655,7 @@ unsigned stem_x6_grid(const StemX6Args &a) { return (unsigned)(a.ntiles < cu_cou
 namespace bev {
 int conv_x6_tune(int knob, int value) {
     if (knob == BEV_TUNE_CONV_X6_TILE) return swap_knob(g_x6_tile, value, 2);
+    if (knob == BEV_TUNE_CONV_X6_STRIP) return swap_knob(g_x6_strip, value, 1);
     return swap_knob(knob == BEV_TUNE_CONV_X6_NT ? g_x6_nt : g_x6_kernel, value, 1);
 }
 }  // namespace bev
