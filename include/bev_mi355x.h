@@ -107,7 +107,11 @@ const char *bev_build_source_hash(void);
  * BEV_TUNE_CONV_X6_STRIP: chained bottleneck bodies (bev_conv2d_chain_x6_f32 / _dual_) with a pre-split operand, a
  *   3x3 / stride 1 / pad 1 conv2 over 64 channels and a 64-channel h2 (ResNet layer1): 1 (default) = conv2's operand
  *   staged once per tap row (a strip of 130 pixels serves the three taps of a row), 0 = once per tap.  Same results
- *   bit for bit. */
+ *   bit for bit.
+ * BEV_TUNE_CONV_X6_BUF: split-bf16 convs on an fp32 operand (k_conv_x6 / k_conv_x6b): 1 (default) = the operand and
+ *   the weight fragments are staged by raw buffer loads from a per-workgroup base (32-bit offsets, tap and channel
+ *   offset in the scalar offset, out-of-image lanes out of range) wherever the images one tile can touch stay below
+ *   2 GiB, 0 = 64-bit pointers always.  Dispatch only.  Same results bit for bit. */
 #define BEV_TUNE_CONV_TILE 1
 #define BEV_TUNE_WARP_POOL_KB 2
 #define BEV_TUNE_WARP_KERNEL 3
@@ -128,6 +132,7 @@ const char *bev_build_source_hash(void);
 #define BEV_TUNE_WARP_TILE_BAND 20
 #define BEV_TUNE_CONV_H16_BUF 21
 #define BEV_TUNE_CONV_X6_STRIP 22
+#define BEV_TUNE_CONV_X6_BUF 23
 int bev_tune(int knob, int value);
 
 /* ---------------------------------------------------------------------------

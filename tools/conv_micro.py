@@ -73,7 +73,7 @@ def run_dual(name, iters):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / iters
     flops = 2 * N * Ho * Wo * Co * (Ci + Ci2)
-    byts = 4 * (N * H * W * Ci + N * Ho * Wo * Ci2 + out.numel())
+    byts = 4 * (h.numel() + N * Ho * Wo * Ci2 + out.numel())  # of x2, the pixels that the stride reads
     print(f"{name:8s} {ms * 1e3:8.1f} us  {flops / ms / 1e9:6.1f} TF  {byts / ms / 1e6:7.1f} GB/s(io)", flush=True)
 
 

@@ -292,6 +292,7 @@ TUNE_WARP_SPAN = 19
 TUNE_WARP_TILE_BAND = 20
 TUNE_CONV_H16_BUF = 21
 TUNE_CONV_X6_STRIP = 22
+TUNE_CONV_X6_BUF = 23
 WARP_KERNEL_DMA, WARP_KERNEL_REGISTER = 0, 1
 
 

@@ -1498,7 +1498,7 @@ int bev_tune(int knob, int value) {
     if (knob == BEV_TUNE_CONV_NBUF) return bev::swap_knob(g_conv_nbuf, value, 2);
     if (knob == BEV_TUNE_WGRAD_MFMA) return bev::train_tune(knob, value);
     if (knob == BEV_TUNE_CONV_X6_TILE || knob == BEV_TUNE_CONV_X6_KERNEL || knob == BEV_TUNE_CONV_X6_NT ||
-        knob == BEV_TUNE_CONV_X6_STRIP)
+        knob == BEV_TUNE_CONV_X6_STRIP || knob == BEV_TUNE_CONV_X6_BUF)
         return bev::conv_x6_tune(knob, value);
     if (knob == BEV_TUNE_CONV_H16_KERNEL) return bev::conv_h16_tune(value);
     if (knob == BEV_TUNE_CONV_H16_BUF) return bev::conv_h16_buf_tune(value);

@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "../../include/bev_mi355x.h"
@@ -46,6 +47,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -63,6 +66,45 @@ __device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l)
     const float r = v - (float)h;
     m = (__bf16)r;
     l = (__bf16)(r - (float)m);
+}
+
+// split3 of two elements at once: the same RNE conversions and exact fp32 differences in the same order, written on
+// vectors so that every conversion is one half of a v_cvt_pk_bf16_f32 and every pair of subtractions one v_pk_add_f32
+// (bit-identical to split3 per element, NaN / Inf / subnormal included: tests/test_conv_x6_buf_gpu.py).
+__device__ __forceinline__ void split3x2(f32x2 v, bf16x2 &h, bf16x2 &m, bf16x2 &l) {
+    h = __builtin_convertvector(v, bf16x2);
+    const f32x2 r = v - __builtin_convertvector(h, f32x2);
+    m = __builtin_convertvector(r, bf16x2);
+    l = __builtin_convertvector(r - __builtin_convertvector(m, f32x2), bf16x2);
+}
+// ... of a float4, as the three bf16x4 that the staging and the split epilogue store
+__device__ __forceinline__ void split3x4(f32x4 v, bf16x4 &h, bf16x4 &m, bf16x4 &l) {
+    bf16x2 h0, m0, l0, h1, m1, l1;
+    split3x2((f32x2){v[0], v[1]}, h0, m0, l0);
+    split3x2((f32x2){v[2], v[3]}, h1, m1, l1);
+    h = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
+    m = __builtin_shufflevector(m0, m1, 0, 1, 2, 3);
+    l = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
+}
+
+// Operand staging by raw buffer loads (k_conv_x6 / k_conv_x6b, BUFA).  One descriptor per operand and workgroup, built
+// from readfirstlane'd halves so that the compiler holds it in SGPRs (no waterfall loop around the loads).  The range
+// check of a raw buffer covers the VGPR offset alone, not the SGPR soffset: a lane that must not load carries
+// X6_VOUT, out of range of any descriptor of at most 2^31 - 16 bytes, and the hardware returns zeros -- no pointer
+// select, no branch.
+template <int PB>
+__device__ __forceinline__ auto x6_bload(__amdgpu_buffer_rsrc_t r, int vo, int so) {
+    if constexpr (PB == 16) return __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0);
+    else return __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0);
+}
+constexpr int X6_VOUT = (int)0x80000000;
+constexpr int64_t X6_BUF_MAX = ((int64_t)1 << 31) - 16;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t x6_rsrc(const void *p, int64_t bytes) {
+    const uint64_t u = (uint64_t)(uintptr_t)p;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+    const int nb = __builtin_amdgcn_readfirstlane((int)(bytes < X6_BUF_MAX ? bytes : X6_BUF_MAX));
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)(((uint64_t)hi << 32) | lo), 0, nb, 0x00020000);
 }
 
 // The split product of one 16-deep k slice, c += A B for a 32 x 32 tile: six v_mfma_f32_32x32x16_bf16 over the planes
@@ -209,12 +251,8 @@ __device__ __forceinline__ void x6_epilogue(const ConvX &a, float *lds, const f3
                         o[0] += rr.x, o[1] += rr.y, o[2] += rr.z, o[3] += rr.w;
                     }
                     bf16x4 hv, mv, lv;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        __bf16 h_, m_, l_;
-                        split3(act_c<ACT>(o[u]), h_, m_, l_);
-                        hv[u] = h_, mv[u] = m_, lv[u] = l_;
-                    }
+                    split3x4((f32x4){act_c<ACT>(o[0]), act_c<ACT>(o[1]), act_c<ACT>(o[2]), act_c<ACT>(o[3])}, hv, mv,
+                             lv);
                     __bf16 *yp = a.ys + m * a.Co + n;
                     if (n < a.Co) {
                         *(bf16x4 *)yp = hv;
@@ -248,7 +286,48 @@ __device__ __forceinline__ void x6_epilogue(const ConvX &a, float *lds, const f3
     });
 }
 
-template <int WM, int WN, int TM, int TN, bool DUAL>
+// The addressing of BUFA's A rows, shared by k_conv_x6 and k_conv_x6b.  The descriptor of x starts at the first image
+// the tile touches (n_first = m0 / (Ho Wo)) MINUS the bytes of pad rows and pad pixels, xbias = pad (W + 1) Ci 4: a
+// row's VGPR offset at tap (0, 0), ((n - n_first) H W + iy0 W + ix0) Ci 4 + xbias, is then never negative, the tap
+// and channel part ((ky dil W + kx dil) Ci + ci0) 4 travels in soffset, and the two add up to an address inside the
+// tensor for every lane that is not masked (the bytes in front of the tensor are never read).  conv_x6() sends a
+// call here only if the images one tile can touch, plus xbias, stay below 2^31 - 16 bytes; num_records runs to the
+// tensor's end or to that cap.  Dual form: x2 [N][H2][W2][Ci2], no padding, a descriptor of its own.
+// lin: x is read as the matrix [M][Ci] (1x1 / stride 1 / pad 0, and the dual form's x) -- output row m reads operand
+// row m, so the descriptor starts at the tile's own first row m0 (inside the first image the tile touches: the size
+// rule holds all the more), a row's offset is (m - m0) Ci 4, and the kernel's prologue divides nothing: neither
+// n_first nor a row's (n, oy, ox) is needed.
+struct X6Desc {
+    __amdgpu_buffer_rsrc_t rx, rx2;
+    int64_t n_first;
+    int xbias;
+    bool lin;
+};
+template <bool DUAL>
+__device__ __forceinline__ X6Desc x6_desc(const ConvX &a, int64_t m0) {
+    X6Desc d;
+    d.lin = DUAL || (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0);
+    d.n_first = 0;
+    d.xbias = 0;
+    if (d.lin) {
+        d.rx = x6_rsrc(a.x + m0 * a.Ci, (a.M - m0) * a.Ci * 4);
+    } else {
+        d.n_first = m0 / ((int64_t)a.Ho * a.Wo);
+        d.xbias = a.pad * (a.W + 1) * a.Ci * 4;
+        const int64_t img = (int64_t)a.H * a.W * a.Ci * 4;
+        d.rx = x6_rsrc((const char *)a.x + d.n_first * img - d.xbias, (a.N - d.n_first) * img + d.xbias);
+    }
+    if (DUAL) {
+        d.n_first = m0 / ((int64_t)a.Ho * a.Wo);
+        const int64_t img2 = (int64_t)a.H2 * a.W2 * a.Ci2 * 4;
+        d.rx2 = x6_rsrc((const char *)a.x2 + d.n_first * img2, (a.N - d.n_first) * img2);
+    } else {
+        d.rx2 = d.rx;
+    }
+    return d;
+}
+
+template <int WM, int WN, int TM, int TN, bool DUAL, bool BUFA = false>
 __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     constexpr int APL = BM * XROW, BPL = BN * XROW;  // bf16 per operand plane
@@ -280,10 +359,25 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
     int64_t pb[AQ], p2[AQ];
     int iy0[AQ], ix0[AQ];
     bool rok[AQ];
+    // BUFA: row q's byte offsets at tap (0, 0) in x / x2 (see X6Desc), and the offset its next load uses: vr, or
+    // X6_VOUT while the row (m >= M) or its tap (outside the image) reads zeros
+    X6Desc dsc;
+    if constexpr (BUFA) dsc = x6_desc<DUAL>(a, m0);
+    unsigned vr[AQ], vr2[AQ];
+    int vo[AQ], vo2[AQ];
 #pragma unroll
     for (int q = 0; q < AQ; ++q) {
         const int64_t m = m0 + (tid >> 2) + 64 * q;
         rok[q] = m < a.M;
+        if constexpr (BUFA && !DUAL) {
+            if (dsc.lin) {  // wave-uniform: no division in this prologue
+                vr[q] = (unsigned)((tid >> 2) + 64 * q) * (unsigned)a.Ci * 4u + 16u * aq;
+                vr2[q] = 0;
+                iy0[q] = ix0[q] = 0;
+                pb[q] = p2[q] = 0;
+                continue;
+            }
+        }
         const int64_t mm = rok[q] ? m : 0;
         const int ox = (int)(mm % a.Wo);
         const int64_t t = mm / a.Wo;
@@ -299,9 +393,24 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
             iy0[q] = oy * a.stride - a.pad;
             ix0[q] = ox * a.stride - a.pad;
         }
+        if constexpr (BUFA) {  // 32-bit byte offsets from the descriptors' bases (wrapping arithmetic for dead rows)
+            const unsigned nr = (unsigned)(int)(n - dsc.n_first);
+            if (DUAL) {
+                vr[q] = (unsigned)(int)(m - m0) * (unsigned)a.Ci * 4u + 16u * aq;
+                vr2[q] = ((nr * a.H2 + (unsigned)(oy * a.stride2)) * a.W2 + (unsigned)(ox * a.stride2)) *
+                             (unsigned)a.Ci2 * 4u + 16u * aq;
+            } else {
+                vr[q] = ((nr * a.H + (unsigned)iy0[q]) * a.W + (unsigned)ix0[q]) * (unsigned)a.Ci * 4u + 16u * aq +
+                        (unsigned)dsc.xbias;
+                vr2[q] = 0;
+            }
+        }
     }
     const int64_t bstep = 3 * 512;  // bf16 per 16-deep slice of a 32-column block (fragment-order panel)
     const __bf16 *brow[BQ];
+    int bvo[BQ];
+    __amdgpu_buffer_rsrc_t rw;
+    if constexpr (BUFA) rw = x6_rsrc(a.wp, copad_x(a.Co) * (int64_t)a.Kp * 6);
     int bdst[BQ];  // LDS offset (bf16) of the piece inside the B part of a stage
 #pragma unroll
     for (int i = 0; i < BQ; ++i) {
@@ -309,6 +418,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
         const int row = pc / PPR, byte = (pc % PPR) * PB;  // byte of the row's 96-B (plane, 16 k) run
         const int pl = byte / 32, hk = (byte % 32) / 16, sub = (byte % 16) / 2;
         brow[i] = a.wp + frag_index(n0 + row, 8 * hk, pl, a.Kp / XBK) + sub;
+        bvo[i] = (int)((frag_index(n0 + row, 8 * hk, pl, a.Kp / XBK) + sub) * 2);  // BUFA: its byte offset in the panel
         bdst[i] = pl * BPL + row * XROW + 8 * hk + sub;
     }
     f32x16 acc[TM][TN];
@@ -321,8 +431,53 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
     bpiece vb0[BQ], vb1[BQ];
     int ky = 0, kx = 0, ci0 = 0, k0 = 0;  // tap / channel (or dual k) of the step being loaded
     int64_t kb = 0;                       // bf16 offset of that step in a panel row
+    // BUFA: the byte offset of tap (ky, kx) (wave-uniform, for soffset) and the rows' validity there -- once per tap,
+    // Ci / 16 K steps share it; a 1x1 conv computes it here and never again
+    int soff = 0;
+    auto x6_tap = [&]() {
+        const int dy = ky * a.dil, dx = kx * a.dil;
+        soff = (dy * a.W + dx) * a.Ci * 4;
+#pragma unroll
+        for (int q = 0; q < AQ; ++q) {
+            const int iy = iy0[q] + dy, ix = ix0[q] + dx;
+            // & not &&: three compares and one select, no branch and no exec-masked region
+            const bool in = rok[q] & ((unsigned)iy < (unsigned)a.H) & ((unsigned)ix < (unsigned)a.W);
+            vo[q] = in ? (int)vr[q] : X6_VOUT;
+            vo2[q] = rok[q] ? (int)vr2[q] : X6_VOUT;
+        }
+    };
+    if constexpr (BUFA) x6_tap();
 #define X6_GLOAD(VA, VB)                                                                                   \
     do {                                                                                                   \
+        if constexpr (BUFA) {                                                                              \
+            if (DUAL) {                                                                                    \
+                if (k0 < a.Ci) {                                                                           \
+                    _Pragma("unroll") for (int q = 0; q < AQ; ++q) VA[q] = __builtin_bit_cast(             \
+                        f32x4, __builtin_amdgcn_raw_buffer_load_b128(dsc.rx, vo[q], k0 * 4, 0));           \
+                } else {                                                                                   \
+                    _Pragma("unroll") for (int q = 0; q < AQ; ++q) VA[q] = __builtin_bit_cast(             \
+                        f32x4, __builtin_amdgcn_raw_buffer_load_b128(dsc.rx2, vo2[q], (k0 - a.Ci) * 4, 0)); \
+                }                                                                                          \
+                k0 += XBK;                                                                                 \
+            } else {                                                                                       \
+                _Pragma("unroll") for (int q = 0; q < AQ; ++q) VA[q] = __builtin_bit_cast(                 \
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(dsc.rx, vo[q], soff, 0));                 \
+                soff += XBK * 4;                                                                           \
+                ci0 += XBK;                                                                                \
+                if (ci0 == a.Ci) {                                                                         \
+                    ci0 = 0;                                                                               \
+                    if (++kx == a.KW) {                                                                    \
+                        kx = 0;                                                                            \
+                        ++ky;                                                                              \
+                    }                                                                                      \
+                    x6_tap();                                                                              \
+                }                                                                                          \
+            }                                                                                              \
+            _Pragma("unroll") for (int i = 0; i < BQ; ++i) VB[i] = __builtin_bit_cast(                     \
+                bpiece, x6_bload<PB>(rw, bvo[i], (int)kb * 2));                                            \
+            kb += bstep;                                                                                   \
+            break;                                                                                         \
+        }                                                                                                  \
         if (DUAL) {                                                                                        \
             const bool first = k0 < a.Ci;                                                                  \
             const float *src = first ? a.x + k0 : a.x2 + (k0 - a.Ci);                                      \
@@ -354,13 +509,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6(ConvX a) {
         __bf16 *Bs = As + 3 * APL;                                                                         \
         _Pragma("unroll") for (int q = 0; q < AQ; ++q) {                                                   \
             bf16x4 hv, mv, lv;                                                                             \
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                \
-                __bf16 h_, m_, l_;                                                                         \
-                split3(VA[q][e], h_, m_, l_);                                                              \
-                hv[e] = h_;                                                                                \
-                mv[e] = m_;                                                                                \
-                lv[e] = l_;                                                                                \
-            }                                                                                              \
+            split3x4(VA[q], hv, mv, lv);                                                                   \
             __bf16 *d = As + ((tid >> 2) + 64 * q) * XROW + 4 * aq;                                        \
             *(bf16x4 *)d = hv;                                                                             \
             *(bf16x4 *)(d + APL) = mv;                                                                     \
@@ -529,13 +678,18 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
                 const int col = wn * TN * 32 + j * 32 + r32;
                 const float bj = a.bias ? a.bias[col] : 0.0f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    __bf16 h_, m_, l_;
-                    split3(act_c<decltype(ac)::value>(acc[i][j][r] + bj), h_, m_, l_);
-                    const int row = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    H[row * HR + col] = h_;
-                    H[HPL + row * HR + col] = m_;
-                    H[2 * HPL + row * HR + col] = l_;
+                for (int r = 0; r < 16; r += 2) {  // two rows (r, r + 1) per split3x2
+                    bf16x2 h_, m_, l_;
+                    split3x2((f32x2){act_c<decltype(ac)::value>(acc[i][j][r] + bj),
+                                     act_c<decltype(ac)::value>(acc[i][j][r + 1] + bj)},
+                             h_, m_, l_);
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int row = wm * TM * 32 + i * 32 + ((r + e) & 3) + 8 * ((r + e) >> 2) + 4 * hh;
+                        H[row * HR + col] = h_[e];
+                        H[HPL + row * HR + col] = m_[e];
+                        H[2 * HPL + row * HR + col] = l_[e];
+                    }
                 }
             }
     });
@@ -643,7 +797,8 @@ constexpr int YBK = 32;
 constexpr int YROW = 40;
 
 // CHAIN: 0 none, 1 chain, 2 chain + shortcut; NT: non-temporal activation loads (BEV_TUNE_CONV_X6_NT)
-template <int WM, int WN, int TM, int TN, bool DUAL, int CHAIN = 0, bool NT = false>
+// BUFA: operand and weight fragments by raw buffer loads (X6Desc above; BEV_TUNE_CONV_X6_BUF), else 64-bit pointers
+template <int WM, int WN, int TM, int TN, bool DUAL, int CHAIN = 0, bool NT = false, bool BUFA = false>
 __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     constexpr int APL = BM * YROW;                 // bf16 per A plane
@@ -666,10 +821,25 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
     int64_t pb[AQ], p2[AQ];
     int iy0[AQ], ix0[AQ];
     bool rok[AQ];
+    // BUFA: row q's byte offsets at tap (0, 0) in x / x2 (see X6Desc), and the offset its next load uses: vr, or
+    // X6_VOUT while the row (m >= M) or its tap (outside the image) reads zeros
+    X6Desc dsc;
+    if constexpr (BUFA) dsc = x6_desc<DUAL>(a, m0);
+    unsigned vr[AQ], vr2[AQ];
+    int vo[AQ], vo2[AQ];
 #pragma unroll
     for (int q = 0; q < AQ; ++q) {
         const int64_t m = m0 + (tid >> 3) + 32 * q;
         rok[q] = m < a.M;
+        if constexpr (BUFA && !DUAL) {
+            if (dsc.lin) {  // wave-uniform: no division in this prologue
+                vr[q] = (unsigned)((tid >> 3) + 32 * q) * (unsigned)a.Ci * 4u + 16u * aq;
+                vr2[q] = 0;
+                iy0[q] = ix0[q] = 0;
+                pb[q] = p2[q] = 0;
+                continue;
+            }
+        }
         const int64_t mm = rok[q] ? m : 0;
         const int ox = (int)(mm % a.Wo);
         const int64_t t = mm / a.Wo;
@@ -685,12 +855,29 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
             iy0[q] = oy * a.stride - a.pad;
             ix0[q] = ox * a.stride - a.pad;
         }
+        if constexpr (BUFA) {  // 32-bit byte offsets from the descriptors' bases (wrapping arithmetic for dead rows)
+            const unsigned nr = (unsigned)(int)(n - dsc.n_first);
+            if (DUAL) {
+                vr[q] = (unsigned)(int)(m - m0) * (unsigned)a.Ci * 4u + 16u * aq;
+                vr2[q] = ((nr * a.H2 + (unsigned)(oy * a.stride2)) * a.W2 + (unsigned)(ox * a.stride2)) *
+                             (unsigned)a.Ci2 * 4u + 16u * aq;
+            } else {
+                vr[q] = ((nr * a.H + (unsigned)iy0[q]) * a.W + (unsigned)ix0[q]) * (unsigned)a.Ci * 4u + 16u * aq +
+                        (unsigned)dsc.xbias;
+                vr2[q] = 0;
+            }
+        }
     }
     // B: this wave's fragments of column blocks (n0 + wn TN 32) / 32 + j; slice g of block cb, plane p at
     // wb + (cb_rel * S + g) * 1536 + p * 512 (bf16), lane part l * 8
     const int64_t S = a.Kp / XBK;
     const __bf16 *wb = a.wp + ((int64_t)((n0 + wn * TN * 32) >> 5) * S) * 1536 + lane * 8;
     const int nslice = a.Kp / XBK;
+    // BUFA: the fragments by raw buffer loads, the lane part of the address in the VGPR offset and the (block, slice,
+    // plane) part in soffset, as k_conv_x6s loads them
+    __amdgpu_buffer_rsrc_t rw;
+    if constexpr (BUFA) rw = x6_rsrc(a.wp, copad_x(a.Co) / 32 * (int64_t)nslice * 3072);
+    const int cb0 = (n0 + wn * TN * 32) >> 5;
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -701,8 +888,51 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
     f32x4 va0[AQ], va1[AQ];
     bf16x8 bs0[TN][3], bs1[TN][3];  // B fragments of the even / odd slices
     int ky = 0, kx = 0, ci0 = 0, k0 = 0;
+    // BUFA: the byte offset of tap (ky, kx) (wave-uniform, for soffset) and the rows' validity there -- once per tap,
+    // Ci / 32 K steps share it; a 1x1 conv computes it here and never again
+    int soff = 0;
+    auto x6_tap = [&]() {
+        const int dy = ky * a.dil, dx = kx * a.dil;
+        soff = (dy * a.W + dx) * a.Ci * 4;
+#pragma unroll
+        for (int q = 0; q < AQ; ++q) {
+            const int iy = iy0[q] + dy, ix = ix0[q] + dx;
+            // & not &&: three compares and one select, no branch and no exec-masked region
+            const bool in = rok[q] & ((unsigned)iy < (unsigned)a.H) & ((unsigned)ix < (unsigned)a.W);
+            vo[q] = in ? (int)vr[q] : X6_VOUT;
+            vo2[q] = rok[q] ? (int)vr2[q] : X6_VOUT;
+        }
+    };
+    if constexpr (BUFA) x6_tap();
+    constexpr int AUX = NT ? 2 : 0;  // the buffer load's cache policy: nt
 #define X6B_GLOAD(VA)                                                                                      \
     do {                                                                                                   \
+        if constexpr (BUFA) {                                                                              \
+            if (DUAL) {                                                                                    \
+                if (k0 < a.Ci) {                                                                           \
+                    _Pragma("unroll") for (int q = 0; q < AQ; ++q) VA[q] = __builtin_bit_cast(             \
+                        f32x4, __builtin_amdgcn_raw_buffer_load_b128(dsc.rx, vo[q], k0 * 4, AUX));         \
+                } else {                                                                                   \
+                    _Pragma("unroll") for (int q = 0; q < AQ; ++q) VA[q] = __builtin_bit_cast(             \
+                        f32x4, __builtin_amdgcn_raw_buffer_load_b128(dsc.rx2, vo2[q], (k0 - a.Ci) * 4, AUX)); \
+                }                                                                                          \
+                k0 += YBK;                                                                                 \
+            } else {                                                                                       \
+                _Pragma("unroll") for (int q = 0; q < AQ; ++q) VA[q] = __builtin_bit_cast(                 \
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(dsc.rx, vo[q], soff, AUX));               \
+                soff += YBK * 4;                                                                           \
+                ci0 += YBK;                                                                                \
+                if (ci0 == a.Ci) {                                                                         \
+                    ci0 = 0;                                                                               \
+                    if (++kx == a.KW) {                                                                    \
+                        kx = 0;                                                                            \
+                        ++ky;                                                                              \
+                    }                                                                                      \
+                    x6_tap();                                                                              \
+                }                                                                                          \
+            }                                                                                              \
+            break;                                                                                         \
+        }                                                                                                  \
         if (DUAL) {                                                                                        \
             const bool first = k0 < a.Ci;                                                                  \
             const float *src = first ? a.x + k0 : a.x2 + (k0 - a.Ci);                                      \
@@ -733,13 +963,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
         __bf16 *As = lds + (BUF) * STAGE;                                                                  \
         _Pragma("unroll") for (int q = 0; q < AQ; ++q) {                                                   \
             bf16x4 hv, mv, lv;                                                                             \
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                \
-                __bf16 h_, m_, l_;                                                                         \
-                split3(VA[q][e], h_, m_, l_);                                                              \
-                hv[e] = h_;                                                                                \
-                mv[e] = m_;                                                                                \
-                lv[e] = l_;                                                                                \
-            }                                                                                              \
+            split3x4(VA[q], hv, mv, lv);                                                                   \
             __bf16 *d = As + ((tid >> 3) + 32 * q) * YROW + 4 * aq;                                        \
             *(bf16x4 *)d = hv;                                                                             \
             *(bf16x4 *)(d + APL) = mv;                                                                     \
@@ -750,8 +974,12 @@ __global__ __launch_bounds__(256, 2) void k_conv_x6b(ConvX a) {
     do {                                                                                                   \
         const int g_ = (G) < nslice ? (G) : nslice - 1; /* past the end: a harmless re-read */             \
         _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                     \
-            _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                  \
-                BS[j][p] = *(const bf16x8 *)(wb + ((int64_t)j * S + g_) * 1536 + p * 512);                \
+            _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                                \
+                if constexpr (BUFA)                                                                        \
+                    BS[j][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(           \
+                                                              rw, lane * 16, (((cb0 + j) * nslice + g_) * 3 + p) * 1024, 0)); \
+                else BS[j][p] = *(const bf16x8 *)(wb + ((int64_t)j * S + g_) * 1536 + p * 512);           \
+            }                                                                                              \
     } while (0)
     const int r32 = lane & 31, h = lane >> 5;
 #define X6B_SLICE(AS, KK, BC)                                                                              \
@@ -1137,19 +1365,26 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
 }
 
 __global__ void k_split3(const float *__restrict__ x, int64_t n, __bf16 *__restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t t = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);  // elements t, t + 1
     if (t >= n) return;
-    __bf16 h, m, l;
-    split3(x[t], h, m, l);
-    out[t] = h;
-    out[t + n] = m;
-    out[t + 2 * n] = l;
+    const bool two = t + 1 < n;
+    bf16x2 h, m, l;
+    split3x2((f32x2){x[t], two ? x[t + 1] : 0.0f}, h, m, l);
+    out[t] = h[0];
+    out[t + n] = m[0];
+    out[t + 2 * n] = l[0];
+    if (two) {
+        out[t + 1] = h[1];
+        out[t + 1 + n] = m[1];
+        out[t + 1 + 2 * n] = l[1];
+    }
 }
 
 int g_x6_tile = 0;  // 0 automatic, 1 = 128 x 128, 2 = 128 x 64
 int g_x6_nt = 0;    // BEV_TUNE_CONV_X6_NT: 1 = non-temporal activation loads in the 32-deep kernels
 int g_x6_kernel = 0;  // 0 automatic (k_conv_x6b wherever it applies), 1 = k_conv_x6 (16-deep K steps) everywhere
 int g_x6_strip = 1;   // BEV_TUNE_CONV_X6_STRIP: 1 = the strip-staged mainloop in the layer1 chains, 0 = one staging per tap
+int g_x6_buf = 1;     // BEV_TUNE_CONV_X6_BUF: 1 = fp32 operands staged by raw buffer loads where the size rule holds
 
 // one workgroup per BM x BN output tile; `kernel` = the k_conv_x6 / k_conv_x6b / k_conv_x6s instance with that tile
 // (BM = WM TM 32, BN = WN TN 32)
@@ -1230,14 +1465,28 @@ int conv_x6(const X6Call &c, hipStream_t st) {
     // The layer1 shape of a pre-split operand (3x3 / 1 / 1 over 64 channels, 128 x 64 tile): one strip per tap row.
     const bool strip = g_x6_strip && c.xs && c.KH == 3 && c.KW == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 &&
                        c.Ci == 64;
+    // An fp32 operand (k_conv_x6 / k_conv_x6b) is staged by raw buffer loads (BUFA) where 32-bit offsets from a
+    // per-workgroup base reach everything one tile can touch: span images of x (a tile of BM <= 128 output pixels
+    // lies in at most BM / (Ho Wo) + 2 images) plus the padding bias of X6Desc, the same for x2, each below
+    // 2^31 - 16 bytes, and a panel below 2 GiB.  Otherwise, and with BEV_TUNE_CONV_X6_BUF = 0, the pointer form.
+    const int64_t span = std::min<int64_t>(c.N, 128 / ((int64_t)c.Ho * c.Wo) + 2);
+    const int64_t kp2 = kpad_x(c.form == X6_DUAL ? c.Ci + c.Ci2 : c.Ci * c.KH * c.KW);
+    const bool buf = g_x6_buf && c.x &&
+                     span * c.H * c.W * c.Ci * 4 + (int64_t)c.pad * (c.W + 1) * c.Ci * 4 < X6_BUF_MAX &&
+                     (!second || span * c.H2 * c.W2 * c.Ci2 * 4 < X6_BUF_MAX) &&
+                     copad_x(c.Co) * kp2 * 6 < ((int64_t)1 << 31);
+#define X6_PICK(K, ...) (buf ? K<__VA_ARGS__, true> : K<__VA_ARGS__, false>)
     if (c.form == X6_CHAIN_DUAL && strip) return launch_x6(k_conv_x6s<4, 1, 1, 2, 2, true>, 128, 64, a, st);
     if (c.form == X6_CHAIN_DUAL)
-        return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 2> : k_conv_x6b<4, 1, 1, 2, false, 2>, 128, 64, a, st);
+        return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 2> : X6_PICK(k_conv_x6b, 4, 1, 1, 2, false, 2, false), 128, 64, a,
+                         st);
     if (c.form == X6_CHAIN && c.Co == 64 && strip) return launch_x6(k_conv_x6s<4, 1, 1, 2, 1, true>, 128, 64, a, st);
     if (c.form == X6_CHAIN && c.Co == 64)
-        return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 1> : k_conv_x6b<4, 1, 1, 2, false, 1>, 128, 64, a, st);
+        return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 1> : X6_PICK(k_conv_x6b, 4, 1, 1, 2, false, 1, false), 128, 64, a,
+                         st);
     if (c.form == X6_CHAIN)
-        return launch_x6(c.xs ? k_conv_x6s<2, 2, 1, 2, 1> : k_conv_x6b<2, 2, 1, 2, false, 1>, 64, 128, a, st);
+        return launch_x6(c.xs ? k_conv_x6s<2, 2, 1, 2, 1> : X6_PICK(k_conv_x6b, 2, 2, 1, 2, false, 1, false), 64, 128, a,
+                         st);
     // One conv (plain, dual): the 128 x 64 tile (t == 2) up to 64 output channels, else 128 x 128
     const bool dual = c.form == X6_DUAL;
     a.nta = g_x6_nt;
@@ -1248,12 +1497,20 @@ int conv_x6(const X6Call &c, hipStream_t st) {
     // kernel in isolation, but the ResNet-50 encoder (two stream groups) is fastest with the 32-deep kernel
     // everywhere (r03 tools/trunk_ab.py: 16.24 ms vs 16.34 with 1x1 / dual layers on the 16-deep one, 16.43 all)
     const bool wide = a.Ci % YBK == 0 && (!dual || a.Ci2 % YBK == 0) && g_x6_kernel != 1;
-    if (wide && t == 2 && !dual && a.nta) return launch_x6(k_conv_x6b<4, 1, 1, 2, false, 0, true>, 128, 64, a, st);
+    if (wide && t == 2 && !dual && a.nta)
+        return launch_x6(X6_PICK(k_conv_x6b, 4, 1, 1, 2, false, 0, true), 128, 64, a, st);
     if (wide && t == 2)
-        return launch_x6(dual ? k_conv_x6b<4, 1, 1, 2, true> : k_conv_x6b<4, 1, 1, 2, false>, 128, 64, a, st);
-    if (wide) return launch_x6(dual ? k_conv_x6b<2, 2, 2, 2, true> : k_conv_x6b<2, 2, 2, 2, false>, 128, 128, a, st);
-    if (t == 2) return launch_x6(dual ? k_conv_x6<4, 1, 1, 2, true> : k_conv_x6<4, 1, 1, 2, false>, 128, 64, a, st);
-    return launch_x6(dual ? k_conv_x6<2, 2, 2, 2, true> : k_conv_x6<2, 2, 2, 2, false>, 128, 128, a, st);
+        return launch_x6(dual ? X6_PICK(k_conv_x6b, 4, 1, 1, 2, true, 0, false)
+                              : X6_PICK(k_conv_x6b, 4, 1, 1, 2, false, 0, false), 128, 64, a, st);
+    if (wide)
+        return launch_x6(dual ? X6_PICK(k_conv_x6b, 2, 2, 2, 2, true, 0, false)
+                              : X6_PICK(k_conv_x6b, 2, 2, 2, 2, false, 0, false), 128, 128, a, st);
+    if (t == 2)
+        return launch_x6(dual ? X6_PICK(k_conv_x6, 4, 1, 1, 2, true) : X6_PICK(k_conv_x6, 4, 1, 1, 2, false), 128, 64,
+                         a, st);
+    return launch_x6(dual ? X6_PICK(k_conv_x6, 2, 2, 2, 2, true) : X6_PICK(k_conv_x6, 2, 2, 2, 2, false), 128, 128, a,
+                     st);
+#undef X6_PICK
 }
 
 // ---------------------------------------------------------------------------
@@ -1656,6 +1913,7 @@ namespace bev {
 int conv_x6_tune(int knob, int value) {
     if (knob == BEV_TUNE_CONV_X6_TILE) return swap_knob(g_x6_tile, value, 2);
     if (knob == BEV_TUNE_CONV_X6_STRIP) return swap_knob(g_x6_strip, value, 1);
+    if (knob == BEV_TUNE_CONV_X6_BUF) return swap_knob(g_x6_buf, value, 1);
     return swap_knob(knob == BEV_TUNE_CONV_X6_NT ? g_x6_nt : g_x6_kernel, value, 1);
 }
 }  // namespace bev
@@ -1688,7 +1946,7 @@ int bev_conv2d_x6_f32(const float *x, const uint16_t *xs, int N, int H, int W, i
 int bev_split3_f32(const float *x, int64_t n, uint16_t *planes, void *stream) {
     if (!x || !planes || n < 0) return BEV_ERR_ARGS;
     if (n == 0) return 0;
-    hipLaunchKernelGGL(k_split3, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n,
+    hipLaunchKernelGGL(k_split3, dim3((unsigned)((n + 511) / 512)), dim3(256), 0, (hipStream_t)stream, x, n,
                        (__bf16 *)planes);
     return last();
 }

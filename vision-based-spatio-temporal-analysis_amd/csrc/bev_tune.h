@@ -22,7 +22,7 @@ int warp_bwd_pool_floats();
 // knob = BEV_TUNE_WGRAD_MFMA (bev_train.hip).
 int train_tune(int knob, int value);
 
-// BEV_TUNE_CONV_X6_TILE / _KERNEL / _NT / _STRIP (bev_conv_x6.hip).
+// BEV_TUNE_CONV_X6_TILE / _KERNEL / _NT / _STRIP / _BUF (bev_conv_x6.hip).
 int conv_x6_tune(int knob, int value);
 
 // BEV_TUNE_CONV_H16_KERNEL (bev_conv_h16.hip): forward tile width / the 32-deep k_conv_h16 (1); weight gradient: 1 =
