@@ -551,6 +551,36 @@ int bev_detection_match_f32(const float *pred, const int32_t *pred_count, int B,
  * argument checks, and BEV_ERR_ARGS for offsets that decrease or leave [0, N]. */
 int bev_detection_match_host(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
                              const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum);
+/* MODA / MODP scoring: the frame's optimal one-to-one matching instead of the greedy walk of train.py:78-104 -- the
+ * rule under which the multi-camera detection results the reference's README names as its goal ("MODA/MODP 等 MCMT
+ * 评价指标") are reported.  Same buffers, argument rules and status codes as bev_detection_match_f32.  The definition
+ * (this library's): a pair (i, j) of a frame is admissible when d_ij = sqrtf(dx dx + dy dy) (fp32, separately rounded,
+ * as above) satisfies d_ij <= thr32 and is finite; a NaN distance never is.  The comparison is <=, the project's rule
+ * -- MVDet's evaluation script uses < -- so a pair at exactly the threshold may match and then adds 0 to MODP.  The
+ * frame's matching is a set of admissible pairs that uses each prediction and each ground truth at most once, has the
+ * most pairs possible and, among those, the smallest sum of the distances taken as doubles.  counts [B][4] = tp (the
+ * pairs), fp = K - tp, fn = G - tp, status; dist_sum [B] = the matched distances added in a double in ascending
+ * prediction index.  Where several matchings tie, which one is taken is fixed by the solver's lowest-index rule
+ * (csrc/bev_metrics.h) and is the same on the device and on the host; tp is the same for all of them and the sums
+ * differ by double rounding at the most.  From totals over any set of frames, in double, in percent:
+ *   MODA = 100 (1 - (FP + FN) / max(1, GT)),  MODP = 100 (TP - DIST_SUM / match_dist) / max(1, TP),
+ *   precision = 100 TP / max(1, TP + FP),     recall = 100 TP / max(1, GT).
+ * Cardinality is maximal by construction (costs are (dummies, distance sum) pairs compared lexicographically; no
+ * penalty constant).  One launch for the batch, one wave per frame, no allocation, memset or synchronisation; every
+ * output element is written.  status -3 (device entry only): the frame has more than
+ * bev_detection_assign_max_frame() (1024) predictions or ground truths -- tp = fp = fn = 0, dist_sum 0; score it with
+ * the host entry.  workspace: none is needed (bev_detection_assign_workspace_bytes is 0 and the pointer may be null);
+ * a negative workspace_bytes is BEV_ERR_ARGS. */
+int64_t bev_detection_assign_workspace_bytes(int B, int cap, int N);
+int bev_detection_assign_max_frame(void);
+int bev_detection_assign_f32(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
+                             const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+/* The same matching on the CPU from host pointers: the kernel's procedure (csrc/bev_metrics.h, assign_solve) run by
+ * one worker, no HIP call; bit-identical outputs, frames of any size.  The argument checks of
+ * bev_detection_match_host. */
+int bev_detection_assign_host(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
+                              const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum);
 int64_t bev_focal_loss_workspace_bytes(int64_t n);
 int bev_focal_loss_fwd_f32(const float *logits, const float *gt, int64_t n, float alpha, float beta, float *loss,
                            float *inv_norm, void *workspace, int64_t workspace_bytes, void *stream);

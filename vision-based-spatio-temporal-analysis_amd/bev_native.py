@@ -69,6 +69,10 @@ SIGNATURES = {
     "bev_detection_match_workspace_bytes": (_i64, [_i, _i]),
     "bev_detection_match_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _i64, _vp]),
     "bev_detection_match_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
+    "bev_detection_assign_workspace_bytes": (_i64, [_i, _i, _i]),
+    "bev_detection_assign_max_frame": (_i, []),
+    "bev_detection_assign_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _i64, _vp]),
+    "bev_detection_assign_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
     "bev_focal_loss_workspace_bytes": (_i64, [_i64]),
     "bev_focal_loss_fwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "bev_focal_loss_bwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
@@ -1966,6 +1970,7 @@ def centernet_targets_host(boxes, frame, B: int, M: int, bev_hw, bounds, res, ov
 # ---------------------------------------------------------------------------
 MATCH_STATUS_PENDING = -1  # counts[b, 3]: the frame's decode awaits the large path (kept count < 0)
 MATCH_STATUS_OFFSETS = -2  # counts[b, 3]: the frame's ground-truth offsets decrease or leave [0, N]
+MATCH_STATUS_TOO_LARGE = -3  # counts[b, 3], detection_assign only: the frame is beyond the device path; use the host entry
 
 
 def match_thr32(match_dist: float) -> float:
@@ -1980,6 +1985,59 @@ def match_thr32(match_dist: float) -> float:
     return float(t)
 
 
+def _detection_device(name: str, entry: str, pred, pred_count, gt_xy, gt_offset, match_dist: float):
+    """The device entries of the two matching rules share buffers and argument rules (include/bev_mi355x.h)."""
+    _require_gpu(pred, gt_xy)
+    _require_gpu(pred_count, gt_offset, dtypes=(torch.int32,), what="int32")
+    if pred.dim() != 3 or pred.shape[2] != 4 or gt_xy.dim() != 2 or gt_xy.shape[1] != 2:
+        raise ValueError(f"{name} expects pred [B, cap, 4] and gt_xy [N, 2], got {tuple(pred.shape)} "
+                         f"{tuple(gt_xy.shape)}")
+    B, cap, _ = pred.shape
+    N = gt_xy.shape[0]
+    if tuple(pred_count.shape) != (B,) or tuple(gt_offset.shape) != (B + 1,):
+        raise ValueError(f"{name} expects pred_count [{B}] and gt_offset [{B + 1}], got "
+                         f"{tuple(pred_count.shape)} {tuple(gt_offset.shape)}")
+    if len({t.device for t in (pred, pred_count, gt_xy, gt_offset)}) != 1:
+        raise ValueError(f"{name} expects all tensors on one device")
+    pred, pred_count, gt_xy, gt_offset = (t.contiguous() for t in (pred, pred_count, gt_xy, gt_offset))
+    dev = pred.device
+    L = lib()
+    if entry == "bev_detection_match_f32":
+        nbytes = int(L.bev_detection_match_workspace_bytes(B, N))
+    else:
+        nbytes = int(L.bev_detection_assign_workspace_bytes(B, cap, N))
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32) if nbytes else None
+    counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    dist_sum = torch.empty(B, device=dev, dtype=torch.float64)
+    _check(getattr(L, entry)(_ptr(pred), _ptr(pred_count), B, cap, _ptr(gt_xy), _ptr(gt_offset), N,
+                             match_thr32(match_dist), _ptr(counts), _ptr(dist_sum),
+                             _ptr(ws) if ws is not None else None, nbytes, _stream(pred)), entry)
+    return counts, dist_sum
+
+
+def _detection_host(name: str, entry: str, pred, pred_count, gt_xy, gt_offset, match_dist: float):
+    import numpy as np
+    as_np = lambda a, dt: np.ascontiguousarray(a.numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)  # noqa: E731
+    pred, gt_xy = as_np(pred, np.float32), as_np(gt_xy, np.float32)
+    pred_count, gt_offset = as_np(pred_count, np.int32), as_np(gt_offset, np.int32)
+    if pred.ndim != 3 or pred.shape[2] != 4 or gt_xy.ndim != 2 or gt_xy.shape[1] != 2:
+        raise ValueError(f"{name} expects pred [B, cap, 4] and gt_xy [N, 2], got {pred.shape} {gt_xy.shape}")
+    B, cap, _ = pred.shape
+    N = gt_xy.shape[0]
+    if pred_count.shape != (B,) or gt_offset.shape != (B + 1,):
+        raise ValueError(f"{name} expects pred_count [{B}] and gt_offset [{B + 1}], got "
+                         f"{pred_count.shape} {gt_offset.shape}")
+    counts = np.zeros((B, 4), np.int32)
+    dist_sum = np.zeros(B, np.float64)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)  # noqa: E731
+    rc = getattr(lib(), entry)(p(pred), p(pred_count), B, cap, p(gt_xy), p(gt_offset), N, match_thr32(match_dist),
+                               p(counts), p(dist_sum))
+    if rc == BEV_ERR_ARGS:
+        raise ValueError(f"{name}: gt_offset must start at >= 0, never decrease and end at <= N")
+    _check(rc, entry)
+    return counts, dist_sum
+
+
 def detection_match(pred: torch.Tensor, pred_count: torch.Tensor, gt_xy: torch.Tensor, gt_offset: torch.Tensor,
                     match_dist: float):
     """The reference's validation matching (train.py:78-104) for a batch in one launch, no synchronisation: pred
@@ -1987,57 +2045,39 @@ def detection_match(pred: torch.Tensor, pred_count: torch.Tensor, gt_xy: torch.T
     gt_offset [B + 1] int32 (frame b's ground truths are rows gt_offset[b] .. gt_offset[b + 1] - 1), all on the GPU
     -> counts [B, 4] int32 (tp, fp, fn, status) and dist_sum [B] float64 (the matched distances added in prediction
     order) on the GPU.  status: 0 complete, MATCH_STATUS_PENDING, MATCH_STATUS_OFFSETS (include/bev_mi355x.h)."""
-    _require_gpu(pred, gt_xy)
-    _require_gpu(pred_count, gt_offset, dtypes=(torch.int32,), what="int32")
-    if pred.dim() != 3 or pred.shape[2] != 4 or gt_xy.dim() != 2 or gt_xy.shape[1] != 2:
-        raise ValueError(f"detection_match expects pred [B, cap, 4] and gt_xy [N, 2], got {tuple(pred.shape)} "
-                         f"{tuple(gt_xy.shape)}")
-    B, cap, _ = pred.shape
-    N = gt_xy.shape[0]
-    if tuple(pred_count.shape) != (B,) or tuple(gt_offset.shape) != (B + 1,):
-        raise ValueError(f"detection_match expects pred_count [{B}] and gt_offset [{B + 1}], got "
-                         f"{tuple(pred_count.shape)} {tuple(gt_offset.shape)}")
-    if len({t.device for t in (pred, pred_count, gt_xy, gt_offset)}) != 1:
-        raise ValueError("detection_match expects all tensors on one device")
-    pred, pred_count, gt_xy, gt_offset = (t.contiguous() for t in (pred, pred_count, gt_xy, gt_offset))
-    dev = pred.device
-    L = lib()
-    nbytes = int(L.bev_detection_match_workspace_bytes(B, N))
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32) if nbytes else None
-    counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
-    dist_sum = torch.empty(B, device=dev, dtype=torch.float64)
-    _check(L.bev_detection_match_f32(_ptr(pred), _ptr(pred_count), B, cap, _ptr(gt_xy), _ptr(gt_offset), N,
-                                     match_thr32(match_dist), _ptr(counts), _ptr(dist_sum),
-                                     _ptr(ws) if ws is not None else None, nbytes, _stream(pred)),
-           "bev_detection_match_f32")
-    return counts, dist_sum
+    return _detection_device("detection_match", "bev_detection_match_f32", pred, pred_count, gt_xy, gt_offset,
+                             match_dist)
 
 
 def detection_match_host(pred, pred_count, gt_xy, gt_offset, match_dist: float):
     """detection_match on the CPU (bev_detection_match_host: the kernel's per-pair functions compiled for the host; no
     GPU needed): numpy arrays or CPU tensors -> (counts [B, 4] int32, dist_sum [B] float64) numpy arrays, the same
     bits as the device entry."""
-    import numpy as np
-    as_np = lambda a, dt: np.ascontiguousarray(a.numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)  # noqa: E731
-    pred, gt_xy = as_np(pred, np.float32), as_np(gt_xy, np.float32)
-    pred_count, gt_offset = as_np(pred_count, np.int32), as_np(gt_offset, np.int32)
-    if pred.ndim != 3 or pred.shape[2] != 4 or gt_xy.ndim != 2 or gt_xy.shape[1] != 2:
-        raise ValueError(f"detection_match_host expects pred [B, cap, 4] and gt_xy [N, 2], got {pred.shape} "
-                         f"{gt_xy.shape}")
-    B, cap, _ = pred.shape
-    N = gt_xy.shape[0]
-    if pred_count.shape != (B,) or gt_offset.shape != (B + 1,):
-        raise ValueError(f"detection_match_host expects pred_count [{B}] and gt_offset [{B + 1}], got "
-                         f"{pred_count.shape} {gt_offset.shape}")
-    counts = np.zeros((B, 4), np.int32)
-    dist_sum = np.zeros(B, np.float64)
-    p = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)  # noqa: E731
-    rc = lib().bev_detection_match_host(p(pred), p(pred_count), B, cap, p(gt_xy), p(gt_offset), N,
-                                        match_thr32(match_dist), p(counts), p(dist_sum))
-    if rc == BEV_ERR_ARGS:
-        raise ValueError("detection_match_host: gt_offset must start at >= 0, never decrease and end at <= N")
-    _check(rc, "bev_detection_match_host")
-    return counts, dist_sum
+    return _detection_host("detection_match_host", "bev_detection_match_host", pred, pred_count, gt_xy, gt_offset,
+                           match_dist)
+
+
+def detection_assign_max_frame() -> int:
+    """The most predictions, and the most ground truths, of a frame the device entry of detection_assign solves."""
+    return int(lib().bev_detection_assign_max_frame())
+
+
+def detection_assign(pred: torch.Tensor, pred_count: torch.Tensor, gt_xy: torch.Tensor, gt_offset: torch.Tensor,
+                     match_dist: float):
+    """The optimal one-to-one matching per frame (MODA / MODP scoring; include/bev_mi355x.h,
+    bev_detection_assign_f32: the most pairs within match_dist, among those the smallest distance sum) for a batch in
+    one launch, no synchronisation.  The buffers and results of detection_match; status also MATCH_STATUS_TOO_LARGE
+    for a frame beyond detection_assign_max_frame(), which detection_assign_host scores."""
+    return _detection_device("detection_assign", "bev_detection_assign_f32", pred, pred_count, gt_xy, gt_offset,
+                             match_dist)
+
+
+def detection_assign_host(pred, pred_count, gt_xy, gt_offset, match_dist: float):
+    """detection_assign on the CPU (bev_detection_assign_host: the kernel's procedure run by one worker; no GPU
+    needed, any frame size): numpy arrays or CPU tensors -> (counts, dist_sum) numpy arrays, the same bits as the
+    device entry."""
+    return _detection_host("detection_assign_host", "bev_detection_assign_host", pred, pred_count, gt_xy, gt_offset,
+                           match_dist)
 
 
 # ---------------------------------------------------------------------------

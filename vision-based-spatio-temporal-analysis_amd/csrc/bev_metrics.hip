@@ -168,6 +168,82 @@ __global__ __launch_bounds__(MT_T) void k_det_match(const float *__restrict__ pr
     }
 }
 
+// k_det_assign    the optimal matching (MODA / MODP): one wave per frame runs bev_metrics::assign_solve, the very
+// procedure of the host entry, with its 64 lanes as the workers -- each owns the ground truths lane, lane + 64, ...,
+// the one reduction per search step is a lexicographic (k, s, index) minimum over the wave by lane exchanges, and the
+// barriers are those of a one-wave workgroup.  Coordinates, duals, tentative distances and the matching of a frame of
+// up to ASSIGN_DEVICE_MAX x ASSIGN_DEVICE_MAX sit in 59 KiB of LDS; there is no cost matrix and no workspace.
+constexpr int AS_T = 64;
+constexpr int AS_MAX = mt::ASSIGN_DEVICE_MAX;
+
+struct WaveExec {
+    __device__ __forceinline__ int lane() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ int lanes() const { return AS_T; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+    __device__ __forceinline__ mt::Best reduce(mt::Best b) const {
+        for (int off = AS_T / 2; off; off >>= 1) {
+            mt::Best o;
+            o.v.k = __shfl_xor(b.v.k, off, AS_T);
+            o.v.s = __shfl_xor(b.v.s, off, AS_T);
+            o.j = __shfl_xor(b.j, off, AS_T);
+            if (mt::best_before(o, b)) b = o;
+        }
+        return b;  // a total order: every lane holds the same element
+    }
+};
+
+__global__ __launch_bounds__(AS_T) void k_det_assign(const float *__restrict__ pred,
+                                                     const int32_t *__restrict__ pred_count, int cap,
+                                                     const float *__restrict__ gt_xy,
+                                                     const int32_t *__restrict__ gt_offset, int N, float thr32,
+                                                     int32_t *__restrict__ counts, double *__restrict__ dist_sum) {
+    __shared__ double us[AS_MAX], vs[AS_MAX], sps[AS_MAX];
+    __shared__ float px[AS_MAX], py[AS_MAX], gx[AS_MAX], gy[AS_MAX];
+    __shared__ int32_t uk[AS_MAX], vk[AS_MAX], spk[AS_MAX];
+    __shared__ int16_t path[AS_MAX], colrow[AS_MAX], rowcol[AS_MAX];
+    __shared__ uint8_t sc[AS_MAX];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int K = pred_count[b];
+    const int g0 = gt_offset[b], g1 = gt_offset[b + 1];
+    int32_t *out = counts + 4 * (int64_t)b;
+    // wave-uniform from here on
+    int status = K < 0 ? mt::STATUS_PENDING : (g0 < 0 || g1 < g0 || g1 > N) ? mt::STATUS_OFFSETS : mt::STATUS_OK;
+    K = K < cap ? K : cap;
+    const int G = g1 - g0;
+    if (status == mt::STATUS_OK && (K > AS_MAX || G > AS_MAX)) status = mt::STATUS_TOO_LARGE;
+    if (status != mt::STATUS_OK || K == 0 || G == 0) {
+        if (tid == 0) {
+            out[mt::TP] = 0;
+            out[mt::FP] = status == mt::STATUS_OK ? K : 0;
+            out[mt::FN] = status == mt::STATUS_OK ? G : 0;
+            out[mt::STATUS] = status;
+            dist_sum[b] = 0.0;
+        }
+        return;
+    }
+    const float *P = pred + 4 * (int64_t)b * cap;
+    const float *Gt = gt_xy + 2 * (int64_t)g0;
+    for (int i = tid; i < K; i += AS_T) {
+        px[i] = P[4 * (int64_t)i];
+        py[i] = P[4 * (int64_t)i + 1];
+    }
+    for (int j = tid; j < G; j += AS_T) {
+        gx[j] = Gt[2 * (int64_t)j];
+        gy[j] = Gt[2 * (int64_t)j + 1];
+    }
+    const mt::AssignState<int16_t> S = {px, py, gx, gy, uk, vk, spk, us, vs, sps, path, colrow, rowcol, sc};
+    int32_t tp = 0;
+    double sum = 0.0;
+    mt::assign_solve(WaveExec(), S, K, G, thr32, &tp, &sum);  // its first barrier publishes the coordinates
+    if (tid == 0) {
+        out[mt::TP] = tp;
+        out[mt::FP] = K - tp;
+        out[mt::FN] = G - tp;
+        out[mt::STATUS] = mt::STATUS_OK;
+        dist_sum[b] = sum;
+    }
+}
+
 // the checks the entries share; 0 when the arguments are usable
 int check_args(const void *pred, const void *pred_count, int B, int cap, const void *gt_xy, const void *gt_offset,
                int N, const void *counts, const void *dist_sum) {
@@ -235,6 +311,72 @@ int bev_detection_match_host(const float *pred, const int32_t *pred_count, int B
                 ++tp;
                 sum += (double)n.d;
             }
+        }
+        out[mt::TP] = tp;
+        out[mt::FP] = K - tp;
+        out[mt::FN] = G - tp;
+        dist_sum[b] = sum;
+    }
+    return 0;
+}
+
+int64_t bev_detection_assign_workspace_bytes(int B, int cap, int N) {
+    (void)B, (void)cap, (void)N;
+    return 0;  // a frame the kernel takes fits its LDS; a larger one is left to the host entry (STATUS_TOO_LARGE)
+}
+
+int bev_detection_assign_max_frame(void) { return AS_MAX; }
+
+int bev_detection_assign_f32(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
+                             const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum,
+                             void *workspace, int64_t workspace_bytes, void *stream) {
+    const int rc = check_args(pred, pred_count, B, cap, gt_xy, gt_offset, N, counts, dist_sum);
+    if (rc) return rc;
+    if (workspace_bytes < 0) return BEV_ERR_ARGS;
+    (void)workspace;
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(k_det_assign, dim3(B), dim3(AS_T), 0, (hipStream_t)stream, pred, pred_count, cap, gt_xy,
+                       gt_offset, N, thr32, counts, dist_sum);
+    return (int)hipGetLastError();
+}
+
+int bev_detection_assign_host(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
+                              const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum) {
+    const int rc = check_args(pred, pred_count, B, cap, gt_xy, gt_offset, N, counts, dist_sum);
+    if (rc) return rc;
+    if (B == 0) return 0;
+    if (gt_offset[0] < 0 || gt_offset[B] > N) return BEV_ERR_ARGS;
+    for (int b = 0; b < B; ++b)
+        if (gt_offset[b + 1] < gt_offset[b]) return BEV_ERR_ARGS;
+    std::vector<float> px, py, gx, gy;
+    std::vector<int32_t> uk, vk, spk, path, colrow, rowcol;
+    std::vector<double> us, vs, sps;
+    std::vector<uint8_t> sc;
+    for (int b = 0; b < B; ++b) {
+        int32_t *out = counts + 4 * (int64_t)b;
+        out[mt::TP] = out[mt::FP] = out[mt::FN] = 0;
+        out[mt::STATUS] = mt::STATUS_OK;
+        dist_sum[b] = 0.0;
+        if (pred_count[b] < 0) {
+            out[mt::STATUS] = mt::STATUS_PENDING;
+            continue;
+        }
+        const int K = pred_count[b] < cap ? pred_count[b] : cap, G = gt_offset[b + 1] - gt_offset[b];
+        int32_t tp = 0;
+        double sum = 0.0;
+        if (K > 0 && G > 0) {
+            const float *P = pred + 4 * (int64_t)b * cap;
+            const float *Gt = gt_xy + 2 * (int64_t)gt_offset[b];
+            const size_t k = (size_t)K, g = (size_t)G;
+            px.resize(k), py.resize(k), uk.resize(k), us.resize(k), rowcol.resize(k);
+            gx.resize(g), gy.resize(g), vk.resize(g), vs.resize(g), spk.resize(g), path.resize(g), colrow.resize(g);
+            sc.resize(g), sps.resize(k > g ? k : g);
+            for (int i = 0; i < K; ++i) px[i] = P[4 * (int64_t)i], py[i] = P[4 * (int64_t)i + 1];
+            for (int j = 0; j < G; ++j) gx[j] = Gt[2 * (int64_t)j], gy[j] = Gt[2 * (int64_t)j + 1];
+            const mt::AssignState<int32_t> S = {px.data(), py.data(), gx.data(),   gy.data(),     uk.data(),
+                                                vk.data(), spk.data(), us.data(),  vs.data(),     sps.data(),
+                                                path.data(), colrow.data(), rowcol.data(), sc.data()};
+            mt::assign_solve(mt::SerialExec(), S, K, G, thr32, &tp, &sum);
         }
         out[mt::TP] = tp;
         out[mt::FP] = K - tp;
