@@ -581,6 +581,53 @@ int bev_detection_assign_f32(const float *pred, const int32_t *pred_count, int B
  * bev_detection_match_host. */
 int bev_detection_assign_host(const float *pred, const int32_t *pred_count, int B, int cap, const float *gt_xy,
                               const int32_t *gt_offset, int N, float thr32, int32_t *counts, double *dist_sum);
+/* Online tracking of the BEV detections: what the reference's README sets as its phase 3 ("集成一个轻量级的在线跟踪
+ * 算法（如 SORT 或 DeepSORT 的变体）… 稳定输出带有时序和ID信息的行人轨迹") and has no code for.  A SORT-style tracker
+ * on ground-plane points; the procedure is csrc/bev_track.h: per frame predict (constant velocity, one 2 x 2
+ * covariance shared by the axes, double arithmetic), associate (the optimal gated matching of
+ * bev_detection_assign_f32 between the predicted positions as float32 and the detections, same tie rule), update,
+ * delete after more than max_age missed frames (stable compaction), birth from the unmatched finite detections in
+ * detection order, report.  thr32: the largest float32 <= the gate in metres; q_pos, q_vel, r, p0_vel: variances of
+ * the process noise (position, velocity), the measurement and a new track's velocity; min_hits: a track is reported
+ * once it has that many consecutive matches, or while the sequence has seen at most that many frames. */
+typedef struct bev_track_params {
+    float thr32;
+    int32_t max_tracks, max_age, min_hits;
+    double q_pos, q_vel, r, p0_vel;
+} bev_track_params;
+/* The state of one sequence is a blob of bev_track_state_bytes(max_tracks) bytes (max_tracks in 1 ..
+ * bev_track_max_frame() = 1024, else BEV_ERR_ARGS), 16-byte aligned: a header (table size, live count, next id,
+ * frames seen, stalled) and the table; every byte of it is defined, so equal histories give equal blobs.
+ * bev_track_reset queues one small launch that writes an empty blob (no tracks, next id 0, no frame seen, not
+ * stalled), bev_track_reset_host writes the same bytes through a host pointer. */
+int64_t bev_track_state_bytes(int max_tracks);
+int bev_track_max_frame(void);
+int bev_track_reset(void *state, int max_tracks, void *stream);
+int bev_track_reset_host(void *state, int max_tracks);
+/* One launch for S independent sequences of B frames each, no synchronisation, allocation or atomics: pred
+ * [S*B][cap][4] and pred_count [S*B] are bev_decode_nms_f32's boxes / kept buffers read in place (cx, cy of the first
+ * min(count, cap, 1024) rows: decode order, the highest scores), sequence s owning rows s*B .. s*B+B-1 in time order
+ * and the blob at states + s * state_stride_bytes.  Frames before `first` are skipped.  Per frame it reaches: ids
+ * [S*B][1024] int32 (the id of detection c's track, -1 for none, unreported or c past the frame's detections),
+ * track_out [S*B][1024][4] f32 (that track's x, y, vx, vy after the update; zeros with -1), info [S*B][4] int32 =
+ * status, live tracks, born, dropped (unmatched detections that found the table full).  status bits: 1 truncated
+ * (more than 1024 detections, the rest untracked); 2 pending (pred_count < 0, the decode's "finished by the large
+ * path" mark: the frame cannot be skipped, so the blob's stalled word is set and the table keeps the state the frame
+ * before left); 4 stalled (an earlier frame is pending; a launch that finds the word set marks all its frames);
+ * 8 the blob is not one bev_track_reset made for params.max_tracks (nothing written to it).  Only first > 0 clears
+ * the stalled word: the host's replay from the pending frame once its decode is complete.  Checked on the host
+ * before any launch: BEV_ERR_ARGS for a null pointer (pred may be null when cap == 0), negative S, B or cap,
+ * B > 65536, first outside [0, B], a gate that is negative or NaN, a variance that is negative or not finite, r <= 0,
+ * max_tracks outside 1 .. 1024, max_age < 0, min_hits < 1, states or state_stride_bytes not a multiple of 16 or the
+ * stride below bev_track_state_bytes.  S == 0 or B == 0 is a no-op. */
+int bev_track_step_f32(const float *pred, const int32_t *pred_count, int S, int B, int cap, int first,
+                       bev_track_params params, void *states, int64_t state_stride_bytes, int32_t *ids,
+                       float *track_out, int32_t *info, void *stream);
+/* The same on the CPU from host pointers: csrc/bev_track.h run by one worker, no HIP call; ids, track_out, info and
+ * every byte of the blobs are those of the device entry, tied inputs included.  The same argument checks. */
+int bev_track_step_host(const float *pred, const int32_t *pred_count, int S, int B, int cap, int first,
+                        bev_track_params params, void *states, int64_t state_stride_bytes, int32_t *ids,
+                        float *track_out, int32_t *info);
 int64_t bev_focal_loss_workspace_bytes(int64_t n);
 int bev_focal_loss_fwd_f32(const float *logits, const float *gt, int64_t n, float alpha, float beta, float *loss,
                            float *inv_norm, void *workspace, int64_t workspace_bytes, void *stream);

@@ -33,6 +33,13 @@ _i64 = ctypes.c_int64
 _f = ctypes.c_float
 _d = ctypes.c_double
 
+
+class _TrackParamsC(ctypes.Structure):
+    """bev_track_params (include/bev_mi355x.h), passed by value."""
+    _fields_ = [("thr32", _f), ("max_tracks", ctypes.c_int32), ("max_age", ctypes.c_int32),
+                ("min_hits", ctypes.c_int32), ("q_pos", _d), ("q_vel", _d), ("r", _d), ("p0_vel", _d)]
+
+
 # name -> (restype, argtypes); must match include/bev_mi355x.h
 SIGNATURES = {
     "bev_abi_version": (_i, []),
@@ -73,6 +80,12 @@ SIGNATURES = {
     "bev_detection_assign_max_frame": (_i, []),
     "bev_detection_assign_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _i64, _vp]),
     "bev_detection_assign_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
+    "bev_track_state_bytes": (_i64, [_i]),
+    "bev_track_max_frame": (_i, []),
+    "bev_track_reset": (_i, [_vp, _i, _vp]),
+    "bev_track_reset_host": (_i, [_vp, _i]),
+    "bev_track_step_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _TrackParamsC, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "bev_track_step_host": (_i, [_vp, _vp, _i, _i, _i, _i, _TrackParamsC, _vp, _i64, _vp, _vp, _vp]),
     "bev_focal_loss_workspace_bytes": (_i64, [_i64]),
     "bev_focal_loss_fwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "bev_focal_loss_bwd_f32": (_i, [_vp, _vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
@@ -2078,6 +2091,175 @@ def detection_assign_host(pred, pred_count, gt_xy, gt_offset, match_dist: float)
     device entry."""
     return _detection_host("detection_assign_host", "bev_detection_assign_host", pred, pred_count, gt_xy, gt_offset,
                            match_dist)
+
+
+# ---------------------------------------------------------------------------
+# online tracking of the BEV detections (the reference's README, phase 3; csrc/bev_track.h)
+# ---------------------------------------------------------------------------
+# info[f, 0] status bits (include/bev_mi355x.h)
+TRACK_STATUS_OK = 0
+TRACK_STATUS_TRUNCATED = 1  # more than track_max_frame() detections: the first ones (the highest scores) were tracked
+TRACK_STATUS_PENDING = 2    # the frame's decode awaits the large path: not tracked, the sequence is stalled here
+TRACK_STATUS_STALLED = 4    # an earlier frame of the sequence is pending: not tracked
+TRACK_STATUS_BAD_STATE = 8  # the state is not one track_reset made for this max_tracks
+TRACK_INFO = ("status", "live", "born", "dropped")  # info's columns
+
+
+class TrackParams(collections.namedtuple("TrackParams", "gate max_age min_hits q_pos q_vel r p0_vel max_tracks")):
+    """The tracker's parameters (include/bev_mi355x.h, bev_track_params): gate in metres; q_pos, q_vel, r, p0_vel the
+    variances of the process noise (position, velocity), the measurement and a new track's velocity; a track unmatched
+    for more than max_age frames is deleted, one with min_hits consecutive matches is reported.  Validated here:
+    ValueError for what the library would refuse."""
+    __slots__ = ()
+
+    def __new__(cls, gate, max_age, min_hits, q_pos, q_vel, r, p0_vel, max_tracks=1024):
+        import math
+        gate, q_pos, q_vel, r, p0_vel = (float(v) for v in (gate, q_pos, q_vel, r, p0_vel))
+        for name, v in (("max_age", max_age), ("min_hits", min_hits), ("max_tracks", max_tracks)):
+            if int(v) != v:
+                raise ValueError(f"TrackParams: {name} must be an integer, got {v!r}")
+        max_age, min_hits, max_tracks = int(max_age), int(min_hits), int(max_tracks)
+        if math.isnan(gate) or gate < 0:
+            raise ValueError(f"TrackParams: gate must be >= 0, got {gate}")
+        for name, v in (("q_pos", q_pos), ("q_vel", q_vel), ("r", r), ("p0_vel", p0_vel)):
+            if not math.isfinite(v) or v < 0:
+                raise ValueError(f"TrackParams: {name} must be finite and >= 0, got {v}")
+        if r <= 0:
+            raise ValueError("TrackParams: r must be > 0")
+        if not 0 <= max_age < 2 ** 31 or not 1 <= min_hits < 2 ** 31:
+            raise ValueError(f"TrackParams: max_age >= 0 and min_hits >= 1, got {max_age} {min_hits}")
+        if not 1 <= max_tracks <= 1024:
+            raise ValueError(f"TrackParams: max_tracks in 1..1024, got {max_tracks}")
+        return super().__new__(cls, gate, max_age, min_hits, q_pos, q_vel, r, p0_vel, max_tracks)
+
+    def c_struct(self) -> _TrackParamsC:
+        return _TrackParamsC(match_thr32(self.gate), self.max_tracks, self.max_age, self.min_hits, self.q_pos,
+                             self.q_vel, self.r, self.p0_vel)
+
+
+def track_max_frame() -> int:
+    """The most tracks of a table, and the most detections of a frame that are tracked."""
+    return int(lib().bev_track_max_frame())
+
+
+def track_state_bytes(max_tracks: int) -> int:
+    n = int(lib().bev_track_state_bytes(int(max_tracks)))
+    if n < 0:
+        raise ValueError(f"track_state_bytes: max_tracks in 1..{track_max_frame()}, got {max_tracks}")
+    return n
+
+
+def track_reset(state, max_tracks: int):
+    """Empty the state blob(s) [S, bytes] or [bytes] uint8: a device tensor by one small launch per sequence on the
+    current stream (no synchronisation), a CPU tensor or numpy array on the host."""
+    nbytes = track_state_bytes(max_tracks)
+    if isinstance(state, torch.Tensor) and state.is_cuda:
+        rows = state.view(-1, state.shape[-1])
+        if state.dtype != torch.uint8 or not state.is_contiguous() or rows.shape[1] < nbytes or rows.shape[1] % 16:
+            raise ValueError(f"track_reset expects contiguous uint8 blobs of >= {nbytes} bytes, a multiple of 16")
+        with torch.cuda.device(state.device):
+            for s in range(rows.shape[0]):
+                _check(lib().bev_track_reset(_ptr(rows[s]), int(max_tracks), _stream(state)), "bev_track_reset")
+        return state
+    import numpy as np
+    arr = state.numpy() if isinstance(state, torch.Tensor) else state
+    rows = arr.reshape(-1, arr.shape[-1])
+    if arr.dtype != np.uint8 or not arr.flags.c_contiguous or rows.shape[1] < nbytes or rows.shape[1] % 16:
+        raise ValueError(f"track_reset expects contiguous uint8 blobs of >= {nbytes} bytes, a multiple of 16")
+    for s in range(rows.shape[0]):
+        _check(lib().bev_track_reset_host(ctypes.c_void_p(rows[s].ctypes.data), int(max_tracks)),
+               "bev_track_reset_host")
+    return state
+
+
+def track_state(max_tracks: int = 1024, device=None, sequences: int = 1):
+    """Empty tracker state for `sequences` independent sequences: a [sequences, track_state_bytes] uint8 tensor on
+    `device`, or -- device None or the CPU -- a numpy array for track_step_host."""
+    nbytes = track_state_bytes(max_tracks)
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    st = torch.empty(int(sequences), nbytes, dtype=torch.uint8, device=dev)
+    if dev.type == "cpu":
+        st = st.numpy()
+    return track_reset(st, max_tracks)
+
+
+def _track_shapes(name, pred_shape, count_shape, sequences, state_shape, nbytes):
+    if len(pred_shape) != 3 or pred_shape[2] != 4:
+        raise ValueError(f"{name} expects pred [S*B, cap, 4], got {tuple(pred_shape)}")
+    F, cap, _ = pred_shape
+    S = int(sequences)
+    if S < 1 or F % S or tuple(count_shape) != (F,):
+        raise ValueError(f"{name} expects pred_count [{F}] and a frame count divisible by sequences={S}")
+    if len(state_shape) != 2 or state_shape[0] != S or state_shape[1] < nbytes or state_shape[1] % 16:
+        raise ValueError(f"{name} expects states [{S}, >= {nbytes} bytes, a multiple of 16], got {tuple(state_shape)}")
+    return F, cap, S, F // S
+
+
+def track_step(pred: torch.Tensor, pred_count: torch.Tensor, params: TrackParams, states: torch.Tensor,
+               first: int = 0, sequences: int = 1):
+    """One tracker launch on the current stream, no synchronisation (include/bev_mi355x.h, bev_track_step_f32): pred
+    [S*B, cap, 4] fp32 and pred_count [S*B] int32 (the decode's own buffers, read in place; sequence s owns frames
+    s*B .. s*B+B-1 in time order), states [S, bytes] uint8 from track_state, updated in place -> ids [S*B, 1024] int32,
+    tracks [S*B, 1024, 4] fp32 (x, y, vx, vy), info [S*B, 4] int32 (TRACK_INFO) on the device.  first: skip the frames
+    before it and clear a stall -- the replay once a pending frame's decode is complete."""
+    _require_gpu(pred)
+    _require_gpu(pred_count, dtypes=(torch.int32,), what="int32")
+    _require_gpu(states, dtypes=(torch.uint8,), what="uint8")
+    if len({t.device for t in (pred, pred_count, states)}) != 1:
+        raise ValueError("track_step expects all tensors on one device")
+    if not states.is_contiguous():
+        raise ValueError("track_step expects contiguous states (they are updated in place)")
+    F, cap, S, B = _track_shapes("track_step", pred.shape, pred_count.shape, sequences, states.shape,
+                                 track_state_bytes(params.max_tracks))
+    pred, pred_count = pred.contiguous(), pred_count.contiguous()
+    n = track_max_frame()
+    dev = pred.device
+    ids = torch.empty(F, n, device=dev, dtype=torch.int32)
+    tracks = torch.empty(F, n, 4, device=dev, dtype=torch.float32)
+    info = torch.empty(F, 4, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _check(lib().bev_track_step_f32(_ptr(pred), _ptr(pred_count), S, B, cap, int(first), params.c_struct(),
+                                        _ptr(states), states.stride(0), _ptr(ids), _ptr(tracks), _ptr(info),
+                                        _stream(pred)), "bev_track_step_f32")
+    return ids, tracks, info
+
+
+def track_step_host(pred, pred_count, params: TrackParams, states, first: int = 0, sequences: int = 1):
+    """track_step on the CPU (bev_track_step_host: the kernel's procedure run by one worker; no GPU needed): numpy
+    arrays or CPU tensors, states a [S, bytes] uint8 numpy array updated in place -> (ids, tracks, info) numpy arrays,
+    the same bits as the device entry, the states included."""
+    import numpy as np
+    as_np = lambda a, dt: np.ascontiguousarray(a.numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)  # noqa: E731
+    pred, pred_count = as_np(pred, np.float32), as_np(pred_count, np.int32)
+    if not isinstance(states, np.ndarray) or states.dtype != np.uint8 or not states.flags.c_contiguous \
+            or not states.flags.writeable:
+        raise ValueError("track_step_host expects states as a writable contiguous uint8 numpy array")
+    F, cap, S, B = _track_shapes("track_step_host", pred.shape, pred_count.shape, sequences, states.shape,
+                                 track_state_bytes(params.max_tracks))
+    n = track_max_frame()
+    ids = np.empty((F, n), np.int32)
+    tracks = np.empty((F, n, 4), np.float32)
+    info = np.empty((F, 4), np.int32)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)  # noqa: E731
+    _check(lib().bev_track_step_host(p(pred), p(pred_count), S, B, cap, int(first), params.c_struct(), p(states),
+                                     states.strides[0], p(ids), p(tracks), p(info)), "bev_track_step_host")
+    return ids, tracks, info
+
+
+def track_state_view(states, max_tracks: int):
+    """The fields of state blobs [S, bytes] (a numpy array, or a tensor that is copied to the host) by name: header
+    words magic, max_tracks, count, next_id, frames_seen, stalled [S] and the table's x, y, vx, vy, p00, p01, p11
+    (float64) and id, streak, misses, age (int32) [S, max_tracks]; views of a numpy input."""
+    import numpy as np
+    a = states.cpu().numpy() if isinstance(states, torch.Tensor) else states
+    M = int(max_tracks)
+    hdr = a[:, :32].view(np.int32)
+    out = {k: hdr[:, i] for i, k in enumerate(("magic", "max_tracks", "count", "next_id", "frames_seen", "stalled"))}
+    d = a[:, 32:32 + 56 * M].view(np.float64).reshape(-1, 7, M)
+    n = a[:, 32 + 56 * M:32 + 72 * M].view(np.int32).reshape(-1, 4, M)
+    out.update({k: d[:, i] for i, k in enumerate(("x", "y", "vx", "vy", "p00", "p01", "p11"))})
+    out.update({k: n[:, i] for i, k in enumerate(("id", "streak", "misses", "age"))})
+    return out
 
 
 # ---------------------------------------------------------------------------

@@ -36,6 +36,25 @@ def save_predictions_json(boxes_list: Sequence, scores_list: Sequence, save_dir:
     return paths
 
 
+def save_tracks_json(boxes_list: Sequence, scores_list: Sequence, ids_list: Sequence, save_dir: str,
+                     frame_indices: Sequence[int]) -> List[str]:
+    """save_predictions_json's files with the tracker's ids beside the detections (utils.tracking.BEVTracker):
+    frame_{idx:06d}.json holding {"frame_idx", "boxes", "scores", "track_ids": [id or -1 per box]}."""
+    os.makedirs(save_dir, exist_ok=True)
+    paths = []
+    for b, frame_idx in enumerate(frame_indices):
+        ids = [int(v) for v in _rows(ids_list[b])]
+        rec = {"frame_idx": int(frame_idx), "boxes": _rows(boxes_list[b]), "scores": _rows(scores_list[b]),
+               "track_ids": ids}
+        if len(ids) != len(rec["boxes"]):
+            raise ValueError(f"save_tracks_json: frame {frame_idx} has {len(rec['boxes'])} boxes, {len(ids)} ids")
+        path = os.path.join(save_dir, f"frame_{int(frame_idx):06d}.json")
+        with open(path, "w") as f:
+            json.dump(rec, f)
+        paths.append(path)
+    return paths
+
+
 def save_bev_heatmap(heatmap, save_path: str, figsize: Optional[tuple] = (4, 4)) -> None:
     """PNG of a [H, W] (or [B, 1, H, W]: the first frame) heatmap, 'hot' colormap."""
     import matplotlib
