@@ -787,6 +787,18 @@ int bev_conv2d_chain_dual_x6_f32(const float *x, const uint16_t *xs, int N, int 
                                  const uint16_t *packed2, const float *bias2, int Co2, int act2, float *y, int Ho,
                                  int Wo, void *stream);
 
+/* device: bev_conv2d_chain_x6_f32 that also runs the NEXT bottleneck's 1x1 conv1 over its own output, in the chain's
+ * epilogue: y as the chain writes it, and ys3 = act3(y (*) W3' + bias3) as the three bf16 planes [3][N*Ho*Wo][Co3]
+ * that bev_conv2d_x6_f32 writes with ys (16-B aligned) -- bit-identical to that launch over y, which is not read
+ * back for it.  packed3 = the split panel of the [Co3][Co2][1][1] weights.  Only the layer1 body's shape: x NULL and
+ * xs given, 3 x 3 / stride 1 / pad 1, Ci == Co == 64, Co2 % 64 == 0, Co3 == 64; residual [N*Ho*Wo][Co2] or NULL.
+ * (Its name differs from the entry ABI 16 retired, whose transposed conv3 this does not bring back.) */
+int bev_conv2d_chain_conv1_x6_f32(const float *x, const uint16_t *xs, int N, int H, int W, int Ci,
+                                  const uint16_t *packed, const float *bias, int Co, int KH, int KW, int stride,
+                                  int pad, int act, const uint16_t *packed2, const float *bias2, int Co2,
+                                  const float *residual, int act2, float *y, const uint16_t *packed3,
+                                  const float *bias3, int Co3, int act3, uint16_t *ys3, int Ho, int Wo, void *stream);
+
 /* device: the ResNet stem (timm conv1: 7x7, stride 2, pad 3, Ci = 3; cnn_encoder.py:26, the first layer of
  * CNNEncoder._encode_single) in the split arithmetic: x NCHW [N][3][H][W] fp32 images, packed = the split panel of
  * the (BN-folded) [Co][3][7][7] weights (bev_conv_pack_weights_x6, 16-B aligned), Co <= 64; y NHWC [N][Ho][Wo][Co]

@@ -118,6 +118,45 @@ def run_chain_dual(name, iters):
     print(f"{name:8s} {ms * 1e3:8.1f} us  {flops / ms / 1e9:6.1f} TF  {byts / ms / 1e6:7.1f} GB/s(io)", flush=True)
 
 
+# a layer1 chain and the next block's conv1 (bf16x6, pre-split operand): name: (Co2, Co3, H, W) -- one launch
+# (bev_conv2d_chain_conv1_x6_f32) against the chain followed by conv1 reading y back
+PAIR = {
+    "l1.1.pair": (256, 64, 270, 480),
+}
+
+
+def run_pair(name, iters):
+    Co2, Co3, H, W = PAIR[name]
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(0)
+    h = nat.split3(torch.randn(N, H, W, 64, device=dev, generator=g))
+    x = torch.randn(N, H, W, Co2, device=dev, generator=g)
+    p1 = nat.pack_conv_weight_x6(torch.randn(64, 64, 3, 3, device=dev, generator=g) * (2.0 / 576) ** 0.5)
+    p2 = nat.pack_conv_weight_x6(torch.randn(Co2, 64, 1, 1, device=dev, generator=g) * (2.0 / 64) ** 0.5)
+    p3 = nat.pack_conv_weight_x6(torch.randn(Co3, Co2, 1, 1, device=dev, generator=g) * (2.0 / Co2) ** 0.5)
+    b1, b2, b3 = (torch.randn(c, device=dev, generator=g) for c in (64, Co2, Co3))
+    out = torch.empty(N, H, W, Co2, device=dev)
+
+    def two():
+        nat.conv2d_chain_nhwc(h, p1, b1, 64, 3, 3, 1, 1, 1, p2, b2, Co2, 1, residual=x, out=out)
+        return nat.conv2d_nhwc_x6(out, p3, b3, Co3, 1, 1, 1, 0, 1, 1, split_out=True)
+
+    def fused():
+        return nat.conv2d_chain_conv1_x6(h, p1, b1, 64, 3, 3, 1, 1, 1, p2, b2, Co2, 1, p3, b3, Co3, 1, residual=x,
+                                         out=out)
+
+    for what, fn in (("2 launches", two), ("fused", fused)):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"{name:8s} {what:10s} {e0.elapsed_time(e1) / iters * 1e3:8.1f} us", flush=True)
+
+
 def run_chain(name, iters):
     Ci, Co, Co2, H, W = CHAIN[name]
     dev = torch.device("cuda")
@@ -193,7 +232,7 @@ def main():
             print(f"-- round {rnd} {a.knob}={v}")
             for name in a.layers:
                 (run_dual if name in DUAL else run_chain if name in CHAIN else run_chain_dual if name in CHAIN_DUAL
-                 else run)(name, a.iters)
+                 else run_pair if name in PAIR else run)(name, a.iters)
             nat.tune(knob, old)
 
 

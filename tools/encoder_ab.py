@@ -31,9 +31,12 @@ def apply(name, rn):
         rn.pw_stream = name != "nopwstream"
         return
     resnet.SPLIT_CHAIN = True
+    resnet.CHAIN_CONV1 = True
     rn.split_edges = False
     if name == "nosplitchain":
         resnet.SPLIT_CHAIN = False
+    elif name == "nochainconv1":  # layer1.2's conv1 as a launch of its own, not in layer1.1's chain
+        resnet.CHAIN_CONV1 = False
     elif name == "splitedges":
         rn.split_edges = True
     elif name != "base":

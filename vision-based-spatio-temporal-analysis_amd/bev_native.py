@@ -196,6 +196,8 @@ SIGNATURES = {
                                           _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "bev_conv2d_chain_x6_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i,
                                      _vp, _i, _i, _vp]),
+    "bev_conv2d_chain_conv1_x6_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp,
+                                           _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "bev_conv2d_dual_x6_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "bev_adam_table_bytes": (_i64, [_i]),
     "bev_adam_chunk_elems": (_i, []),
@@ -1539,6 +1541,45 @@ def conv2d_chain_nhwc(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, KH: 
                                         _ptr(out), Ho, Wo, _stream(x))
     _check(rc, "bev_conv2d_chain_f32")
     return out
+
+
+CHAIN_CONV1_CO = 64  # the next conv's output channels that bev_conv2d_chain_conv1_x6_f32 is built for
+
+
+def chain_conv1_applies(Ci: int, Co: int, KH: int, KW: int, stride: int, pad: int, Co2: int, Co3: int) -> bool:
+    """The shapes conv2d_chain_conv1_x6 covers: the layer1 bottleneck body (3x3 / 1 / 1 over 64 channels -> 64 ->
+    Co2 in 64s) feeding a 1x1 conv of CHAIN_CONV1_CO output channels."""
+    return (Ci == 64 and Co == 64 and KH == 3 and KW == 3 and stride == 1 and pad == 1 and Co2 > 0 and Co2 % 64 == 0
+            and Co3 == CHAIN_CONV1_CO)
+
+
+def conv2d_chain_conv1_x6(xs: Split3, packed: torch.Tensor, bias, Co: int, KH: int, KW: int, stride: int, pad: int,
+                          relu: int, packed2: torch.Tensor, bias2, Co2: int, relu2: int, packed3: torch.Tensor, bias3,
+                          Co3: int, relu3: int, residual: torch.Tensor = None, out: torch.Tensor = None):
+    """conv2d_chain_nhwc on a pre-split operand in the split arithmetic, and in the same launch the NEXT block's 1x1
+    conv over its output: returns (y, Split3 of act3(y (*) W3' + bias3)), both bit-identical to the chain followed by
+    conv2d_nhwc_x6(y, ..., split_out=True) (bev_conv2d_chain_conv1_x6_f32; y is not read back for the second)."""
+    if not isinstance(xs, Split3) or not xs.planes.is_cuda:
+        raise HipError("conv2d_chain_conv1_x6 needs a pre-split operand on the device")
+    for p in (packed, packed2, packed3):
+        _require_panel(p, torch.bfloat16, "conv2d_chain_conv1_x6")
+    _require_gpu(bias, bias2, bias3, residual)
+    N, H, W, Ci = xs.shape
+    Ho, Wo = _out_hw(H, W, KH, KW, stride, pad)
+    if out is None:
+        out = torch.empty(N, Ho, Wo, Co2, device=xs.device, dtype=torch.float32)
+    assert out.shape == (N, Ho, Wo, Co2) and out.is_contiguous() and out.dtype == torch.float32
+    if residual is not None:
+        residual = residual.contiguous()
+        assert residual.shape == out.shape
+    ys = torch.empty(3, N, Ho, Wo, Co3, device=xs.device, dtype=torch.bfloat16)
+    with _span("conv", xs.planes):
+        rc = lib().bev_conv2d_chain_conv1_x6_f32(None, _ptr(xs.planes), N, H, W, Ci, _ptr(packed), _ptr(bias), Co, KH,
+                                                 KW, stride, pad, int(relu), _ptr(packed2), _ptr(bias2), Co2,
+                                                 _ptr(residual), int(relu2), _ptr(out), _ptr(packed3), _ptr(bias3),
+                                                 Co3, int(relu3), _ptr(ys), Ho, Wo, _stream(xs.planes))
+    _check(rc, "bev_conv2d_chain_conv1_x6_f32")
+    return out, Split3(ys)
 
 
 def conv2d_chain_dual_nhwc(x: torch.Tensor, packed: torch.Tensor, bias, Co: int, KH: int, KW: int, stride: int,

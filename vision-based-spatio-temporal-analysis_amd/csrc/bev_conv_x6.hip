@@ -169,6 +169,10 @@ struct ConvX {  // filled by conv_x6()
     const __bf16 *__restrict__ wp2 = nullptr;
     const float *__restrict__ bias2 = nullptr;
     int Co2 = 0, act2 = 0;
+    // the next block's 1x1 conv1 in the chain's epilogue (x6_chain_epilogue NXT): ys = act3(y (*) W3' + bias3), split
+    const __bf16 *__restrict__ wp3 = nullptr;
+    const float *__restrict__ bias3 = nullptr;
+    int Co3 = 0, act3 = 0;
     int nta = 0;  // 1: A (activation) loads non-temporal (BEV_TUNE_CONV_X6_NT, the last layer of a trunk)
 };
 
@@ -616,7 +620,24 @@ __host__ __device__ constexpr int x6_chain_lds_bytes() { return 3 * BM * (BN + 8
 // once per wave and reused by every block; the panel is the dual tail's [W3 | Wds].
 // Per output element: slices ascending, the six products of a slice in the mainloop's order, (acc + bias2) +
 // residual, then act2 -- the separate launches' arithmetic.
-template <int WM, int WN, int TM, int TN, int X2S = 0>
+// NXT > 0 (the 128 x 64 tile, one step per block; bev_conv2d_chain_conv1_x6_f32): the NEXT block's 1x1 conv1 over
+// y, NXT output channels, runs here too, so y is not read back for it.  A wave's 32 x 32 block of y belongs to the 32
+// rows whose conv1 output it computes, and the block's 32 channels are two 16-deep slices of conv1's K: the block's
+// o (the stored values) is split (split3x2), written as three bf16 planes [32][40] (80-B rows: 5 odd 16-B slots)
+// into a wave-private LDS area and read back as the A fragments of the two slices -- a same-wave round trip, LDS
+// operations of one wave complete in order, no barrier -- then 6 NXT / 32 MFMAs per slice against conv1's panel
+// fragments accumulate into accn.  K order of conv1: blocks ascending, the two slices ascending, x6_dot's products:
+// a 1x1 k_conv_x6b / k_conv_x6s over the same K does exactly that, so h' is bit-identical to the separate launch.
+// conv1's panel runs of a step (2 slices x NXT / 32 column blocks x 3 planes of 1 KiB) are staged like W3, by DMAs
+// issued right behind the step's W3 DMAs into a stage next to the W3 stage.  LDS after the fragments are taken:
+//     [0, 12 K) W3 stage 1 | [12 K, 24 K) conv1 stage 1 | [24 K, 54 K) four y blocks of 7.5 KiB | HB = 54 K:
+//     W3 stage 0 | conv1 stage 0 | 78 K
+// Issue order per step with NXT: wait, barrier | W3 DMAs of step s + 1 | conv1 DMAs of step s + 1 | bias2 + residual
+// of the next block | 24 MFMAs | 16 stores | y block through LDS (lgkmcnt only) | 6 NXT / 16 MFMAs.  Behind a step's
+// DMAs (both kinds together) there are still the R look-ahead loads and the 16 stores: the count R + 16 holds.
+// After the last block: h' = act3(accn + bias3), split, through the same LDS area as 16-B row pieces to the three
+// planes of ys; rows at or past M are not stored.
+template <int WM, int WN, int TM, int TN, int X2S = 0, int NXT = 0>
 __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char *lds_raw, const f32x16 (&acc)[TM][TN],
                                                   int wave, int lane, int wm, int wn, int64_t m0) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32, HR = BN + 8, HPL = BM * HR;
@@ -629,6 +650,11 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
     constexpr int HB = 3 * HPL * 2;  // bytes of the h2 planes = offset of W3 stage 0
     constexpr int PW = WPB * 3;      // 1-KiB DMA pieces per wave and step
     static_assert(HB % 1024 == 0, "W3 stage 0 starts on a fragment boundary");
+    // the next conv: NJ column blocks of 32, a stage of 2 NJ 3 fragment runs, y blocks of three [32][YP] planes
+    constexpr int NJ = NXT / 32, W3B = 12 * WPB * 1024, NXB = 6 * NJ * 1024, YP = 40, YPL = 32 * YP;
+    constexpr int YB0 = W3B + NXB, YBW = 3 * YPL * 2;  // first y block, bytes per wave
+    static_assert(NXT == 0 || (NXT % 64 == 0 && WPB == 1 && U == 1 && X2S == 0), "next conv: the 128 x 64 plain chain");
+    static_assert(NXT == 0 || YB0 + 4 * YBW <= HB, "stages 1 and the y blocks overlay the dead h2 planes");
     __bf16 *H = (__bf16 *)lds_raw;
     const int r32 = lane & 31, hh = lane >> 5;
     const int band = (wave % NB) * 32, part = wave / NB;
@@ -664,12 +690,27 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
                       lbase + sbo + (unsigned)(q * 1024));
         }
     };
+    // NXT: this wave's share of the next conv's runs for y block g (slices 2 g, 2 g + 1 of its K = Co2) -> the stage
+    // behind the W3 stage at sbo: piece q = (column block, slice, plane) is panel run ((cb S3 + 2 g) 3 + q % 6)
+    const __bf16 *nsrc = a.wp3 + lane * 8;
+    auto issue_nx = [&](int g, unsigned sbo) {
+        const int S3 = a.Co2 / 16;
+#pragma unroll
+        for (int i = 0; i < NJ * 6 / 4; ++i) {
+            const int q = wave + 4 * i, cbl = q / 6, r = q % 6;
+            lds_dma16(nsrc + (((int64_t)cbl * S3 + 2 * g) * 3 + r) * 512, lbase + sbo + (unsigned)(W3B + q * 1024));
+        }
+    };
     // first block's residual: requested before the h2 staging, so its latency overlaps it
     float rv[2][17];
     if (a.res) res_load(std::true_type{}, 32 * part, rv[0], true);
     else res_load(std::false_type{}, 32 * part, rv[0], true);
+    float b3[NJ > 0 ? NJ : 1];  // the next conv's bias of this lane's columns
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) b3[j] = a.bias3 ? a.bias3[32 * j + r32] : 0.0f;
     __syncthreads();  // every wave is done with the staging buffers
     issue_w3(0, 0, HB);
+    if constexpr (NXT > 0) issue_nx(0, HB);
     act_dispatch(a.act, [&](auto ac) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -726,6 +767,29 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
     // everything this wave has issued so far is complete: the counted waits of the loop start from an empty queue
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(a.y + base, rows * a.Co2 * 4);
+    // NXT: the wave's LDS block and the next conv's accumulators.  put_block: 16 C-layout values per lane (column r32,
+    // rows (r & 3) + 8 (r >> 2) + 4 hh) split into the three planes; frag: 16-B piece c of row `row`, plane p (A
+    // fragment of slice t: row r32, piece 2 t + hh)
+    __bf16 *Y = (__bf16 *)(lds_raw + YB0 + wave * YBW);
+    f32x16 accn[NJ > 0 ? NJ : 1];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) accn[j] = (f32x16){0};
+    auto put_block = [&](const float(&o)[16]) {
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+            bf16x2 h_, m_, l_;
+            split3x2((f32x2){o[r], o[r + 1]}, h_, m_, l_);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                __bf16 *yp = Y + (((r + e) & 3) + 8 * ((r + e) >> 2) + 4 * hh) * YP + r32;
+                yp[0] = h_[e];
+                yp[YPL] = m_[e];
+                yp[2 * YPL] = l_[e];
+            }
+        }
+        asm volatile("" ::: "memory");  // the reads below follow these writes (one wave: LDS keeps their order)
+    };
+    auto frag = [&](int p, int row, int c) { return *(const bf16x8 *)(Y + p * YPL + row * YP + 8 * c); };
     // one column block: rc = its bias2 / residual (loaded during the previous block), rn = the next block's
     auto block = [&](auto hr, auto a2, int g, float(&rc)[17], float(&rn)[17]) {
         constexpr bool HAS_RES = decltype(hr)::value;
@@ -743,6 +807,9 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
             const unsigned sbo = ((g * U + u) & 1) ? 0u : (unsigned)HB;
             if (u + 1 < U) issue_w3(g, u + 1, (unsigned)HB - sbo);
             else if (more) issue_w3(g + 1, 0, (unsigned)HB - sbo);
+            if constexpr (NXT > 0) {
+                if (more) issue_nx(g + 1, (unsigned)HB - sbo);
+            }
             if (u == 0) {
                 res_load(hr, c0 + 32 * WPB, rn, more);
                 asm volatile("" ::: "memory");  // the loads stay here, in front of the step's LDS reads and MFMAs
@@ -758,13 +825,34 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
             }
         }
         const float bj = rc[16];
+        float ov[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float o = acc2[r] + bj;
             if constexpr (HAS_RES) o += rc[r];
             o = act_c<decltype(a2)::value>(o);
+            ov[r] = o;
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), ry,
                                                   vo + ((r & 3) + 8 * (r >> 2)) * a.Co2 * 4, c0 * 4, 0);
+        }
+        if constexpr (NXT > 0) {  // the next conv over this block's 32 channels of y: slices 2 g, 2 g + 1 of its K
+            put_block(ov);
+            bf16x8 ya[2][3];
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int p = 0; p < 3; ++p) ya[t][p] = frag(p, r32, 2 * t + hh);
+            const unsigned sbo = (g & 1) ? 0u : (unsigned)HB;
+            const __bf16 *Ns = (const __bf16 *)(lds_raw + sbo + W3B) + lane * 8;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    bf16x8 fb[3];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) fb[p] = *(const bf16x8 *)(Ns + ((j * 2 + t) * 3 + p) * 512);
+                    x6_dot(accn[j], ya[t], fb);
+                }
         }
     };
     auto run = [&](auto hr, auto a2) {
@@ -784,6 +872,29 @@ __device__ __forceinline__ void x6_chain_epilogue(const ConvX &a, unsigned char 
         if (a.res) run(std::true_type{}, a2);
         else run(std::false_type{}, a2);
     });
+    if constexpr (NXT > 0) {
+        // h' = act3(accn + bias3), split; through the wave's LDS block (free: the last block's fragments are in
+        // registers) so that a lane stores 16-B row pieces: lane -> (row lane / 4 (+ 16), piece lane % 4), 64 B a row
+        act_dispatch(a.act3, [&](auto a3) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                float ov[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) ov[r] = act_c<decltype(a3)::value>(accn[j][r] + b3[j]);
+                put_block(ov);
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int row = 16 * i + (lane >> 2), c = lane & 3;
+                        const bf16x8 v = frag(p, row, c);
+                        const int64_t m = m0 + band + row;
+                        if (m < a.M) *(bf16x8 *)(a.ys + p * a.yps + m * NXT + 32 * j + 8 * c) = v;
+                    }
+                asm volatile("" ::: "memory");  // the next column block's writes follow these reads
+            }
+        });
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1209,6 +1320,9 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
     static_assert(RW % 16 == 0, "whole DMA groups per wave");
     static_assert(!BLDS || (BN / 32 * 6) % 4 == 0, "whole B pieces per wave");
     static_assert(!STRIP || (CHAIN > 0 && WM == 4 && WN == 1 && TM == 1 && TN == 2), "strip: the 128 x 64 chains");
+    // CHAIN 3: the chain plus the next block's conv1 (x6_chain_epilogue NXT = 64), strip-staged only; its epilogue
+    // puts a conv1 stage behind W3 stage 0: h2 planes + 2 x 12 KiB, exactly the strip mainloop's LDS
+    static_assert(CHAIN != 3 || (STRIP && LDSB >= 3 * BM * (BN + 8) * 2 + 2 * 12288), "next conv: strip form, LDS");
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDSB];
     const __bf16 *lds = (const __bf16 *)lds_raw;
 
@@ -1223,7 +1337,8 @@ __global__ __launch_bounds__(256, CHAIN ? 2 : 3) void k_conv_x6s(ConvX a) {
     if constexpr (STRIP) {  // Ci = Co = 64, 3x3 / 1 / 1 (conv_x6() checks): one column tile, n0 = 0
         f32x16 sacc[1][2] = {{(f32x16){0}, (f32x16){0}}};
         x6s_strip_mainloop(a, lds_raw, sacc, wave, lane, m0);
-        x6_chain_epilogue<WM, WN, TM, TN, CHAIN == 2 ? 4 : 0>(a, lds_raw, sacc, wave, lane, wm, wn, m0);
+        x6_chain_epilogue<WM, WN, TM, TN, CHAIN == 2 ? 4 : 0, CHAIN == 3 ? 64 : 0>(a, lds_raw, sacc, wave, lane, wm, wn,
+                                                                                     m0);
         return;
     }
 
@@ -1398,7 +1513,7 @@ int launch_x6(void (*kernel)(ConvX), int BM, int BN, const ConvX &a, hipStream_t
 // What a tensor entry point asks for.  An entry fills what it has and leaves the rest at these defaults, under which
 // the rules of conv_x6() that do not concern it hold by themselves: a null pointer is aligned, and the dual form's
 // first operand is the 1x1 / stride 1 conv over x [N][Ho][Wo][Ci] that needs no geometry check of its own.
-enum X6Form { X6_PLAIN, X6_DUAL, X6_CHAIN, X6_CHAIN_DUAL };
+enum X6Form { X6_PLAIN, X6_DUAL, X6_CHAIN, X6_CHAIN_DUAL, X6_CHAIN_NEXT };
 struct X6Call {
     X6Form form;
     // the conv (of a chain: the first, conv2 of the bottleneck): exactly one of x (fp32) and xs (pre-split planes)
@@ -1416,14 +1531,24 @@ struct X6Call {
     const uint16_t *packed2 = nullptr;
     const float *bias2 = nullptr;
     int Co2 = 0, act2 = 0;
+    // third conv (chain-next): the next block's 1x1 conv1 over y, its output split into ys ([3][M][Co3])
+    const uint16_t *packed3 = nullptr;
+    const float *bias3 = nullptr;
+    int Co3 = 0, act3 = 0;
 };
 
 // The one host path of the split convs: validates, fills ConvX, picks the kernel instance.
 int conv_x6(const X6Call &c, hipStream_t st) {
-    const bool chain = c.form == X6_CHAIN || c.form == X6_CHAIN_DUAL;
+    const bool next = c.form == X6_CHAIN_NEXT;  // a chain that writes y AND the next conv's split output ys
+    const bool chain = c.form == X6_CHAIN || c.form == X6_CHAIN_DUAL || next;
     const bool second = c.form == X6_DUAL || c.form == X6_CHAIN_DUAL;  // has x2
-    if ((!c.x == !c.xs) || !c.packed || (!c.y == !c.ys) || c.N < 0 || c.H <= 0 || c.W <= 0 || c.Co <= 0 || c.KH <= 0 ||
-        c.KW <= 0 || c.stride <= 0 || c.pad < 0 || c.dil <= 0 || c.act < 0 || c.act > 2)
+    // chain-next: only what its one kernel instance covers (the strip-staged layer1 body, 64 next channels)
+    if (next && (!c.xs || !c.y || !c.ys || !c.packed3 || c.KH != 3 || c.KW != 3 || c.stride != 1 || c.pad != 1 ||
+                 c.Ci != 64 || c.Co != 64 || c.Co3 != 64 || c.act3 < 0 || c.act3 > 2 ||
+                 (((uintptr_t)c.packed3 | (uintptr_t)c.ys) & 15) != 0))
+        return BEV_ERR_ARGS;
+    if ((!c.x == !c.xs) || !c.packed || (!next && !c.y == !c.ys) || c.N < 0 || c.H <= 0 || c.W <= 0 || c.Co <= 0 ||
+        c.KH <= 0 || c.KW <= 0 || c.stride <= 0 || c.pad < 0 || c.dil <= 0 || c.act < 0 || c.act > 2)
         return BEV_ERR_ARGS;
     // one tap and 16 channels per K step; 32 for a pre-split operand and in the chains (k_conv_x6b / k_conv_x6s only).
     // The chains check no more of Ci than this.
@@ -1444,7 +1569,7 @@ int conv_x6(const X6Call &c, hipStream_t st) {
         return BEV_ERR_ARGS;
     // y rows of ldy >= Co floats; dense for a residual and for split output (a chain's y: dense rows of Co2)
     if (!chain && (c.ldy < c.Co || (c.res && c.ldy != c.Co))) return BEV_ERR_ARGS;
-    if (c.ys && (c.ldy != c.Co || c.Co % 4 != 0 || ((uintptr_t)c.ys & 7) != 0)) return BEV_ERR_ARGS;
+    if (!next && c.ys && (c.ldy != c.Co || c.Co % 4 != 0 || ((uintptr_t)c.ys & 7) != 0)) return BEV_ERR_ARGS;
     if (c.N == 0) return 0;
     // two waves share each 32-row band of the 64-row tile (checked behind the empty call's answer: test_capi.py pins it)
     if (c.form == X6_CHAIN && c.Co != 64 && c.Co2 % 128 != 0) return BEV_ERR_ARGS;
@@ -1457,8 +1582,9 @@ int conv_x6(const X6Call &c, hipStream_t st) {
     a.M = (int64_t)c.N * c.Ho * c.Wo;
     a.x2 = c.x2, a.Ci2 = c.Ci2, a.H2 = c.H2, a.W2 = c.W2, a.stride2 = c.stride2;
     a.xs = (const __bf16 *)c.xs, a.ys = (__bf16 *)c.ys;
-    a.xps = (int64_t)c.N * c.H * c.W * c.Ci, a.yps = a.M * c.Co;
+    a.xps = (int64_t)c.N * c.H * c.W * c.Ci, a.yps = a.M * (next ? c.Co3 : c.Co);
     a.wp2 = (const __bf16 *)c.packed2, a.bias2 = c.bias2, a.Co2 = c.Co2, a.act2 = c.act2;
+    a.wp3 = (const __bf16 *)c.packed3, a.bias3 = c.bias3, a.Co3 = c.Co3, a.act3 = c.act3;
 
     // The chains.  A pre-split operand (conv1 handed over its output split) is staged by LDS-DMA (k_conv_x6s), same K
     // order.  h2 of 128 channels: the 64 x 128 tile (h2 planes 52 KiB of LDS).
@@ -1476,6 +1602,8 @@ int conv_x6(const X6Call &c, hipStream_t st) {
                      (!second || span * c.H2 * c.W2 * c.Ci2 * 4 < X6_BUF_MAX) &&
                      copad_x(c.Co) * kp2 * 6 < ((int64_t)1 << 31);
 #define X6_PICK(K, ...) (buf ? K<__VA_ARGS__, true> : K<__VA_ARGS__, false>)
+    // chain-next: its one (strip-staged) instance, whatever BEV_TUNE_CONV_X6_STRIP says
+    if (next) return launch_x6(k_conv_x6s<4, 1, 1, 2, 3, true>, 128, 64, a, st);
     if (c.form == X6_CHAIN_DUAL && strip) return launch_x6(k_conv_x6s<4, 1, 1, 2, 2, true>, 128, 64, a, st);
     if (c.form == X6_CHAIN_DUAL)
         return launch_x6(c.xs ? k_conv_x6s<4, 1, 1, 2, 2> : X6_PICK(k_conv_x6b, 4, 1, 1, 2, false, 2, false), 128, 64, a,
@@ -1970,6 +2098,20 @@ int bev_conv2d_chain_x6_f32(const float *x, const uint16_t *xs, int N, int H, in
     c.N = N, c.H = H, c.W = W, c.Ci = Ci, c.Co = Co, c.KH = KH, c.KW = KW, c.stride = stride, c.pad = pad;
     c.act = act, c.Ho = Ho, c.Wo = Wo;
     c.packed2 = packed2, c.bias2 = bias2, c.Co2 = Co2, c.act2 = act2;
+    return conv_x6(c, (hipStream_t)stream);
+}
+
+int bev_conv2d_chain_conv1_x6_f32(const float *x, const uint16_t *xs, int N, int H, int W, int Ci,
+                                   const uint16_t *packed, const float *bias, int Co, int KH, int KW, int stride,
+                                   int pad, int act, const uint16_t *packed2, const float *bias2, int Co2,
+                                   const float *residual, int act2, float *y, const uint16_t *packed3,
+                                   const float *bias3, int Co3, int act3, uint16_t *ys3, int Ho, int Wo, void *stream) {
+    X6Call c{X6_CHAIN_NEXT};
+    c.x = x, c.xs = xs, c.packed = packed, c.bias = bias, c.res = residual, c.y = y, c.ys = ys3;
+    c.N = N, c.H = H, c.W = W, c.Ci = Ci, c.Co = Co, c.KH = KH, c.KW = KW, c.stride = stride, c.pad = pad;
+    c.act = act, c.Ho = Ho, c.Wo = Wo;
+    c.packed2 = packed2, c.bias2 = bias2, c.Co2 = Co2, c.act2 = act2;
+    c.packed3 = packed3, c.bias3 = bias3, c.Co3 = Co3, c.act3 = act3;
     return conv_x6(c, (hipStream_t)stream);
 }
 

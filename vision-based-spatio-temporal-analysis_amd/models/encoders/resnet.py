@@ -84,6 +84,10 @@ STEM_POOL = True
 # (bev_conv2d_x6_f32 ys) and the chain stages conv2's operand by LDS-DMA with no split in its mainloop (k_conv_x6s
 # CHAIN).  Bit-identical either way; False: conv1 writes fp32 and the chain splits it once per tap (k_conv_x6b).
 SPLIT_CHAIN = True
+# A layer1 chain6 body whose successor block starts with a 1x1 conv1 of 64 channels runs that conv1 in its own epilogue
+# (bev_conv2d_chain_conv1_x6_f32): the block output is written once and read back once (the residual), not twice, and
+# the successor starts from the returned Split3.  Bit-identical; False: the successor launches its conv1 itself.
+CHAIN_CONV1 = True
 
 
 class FoldedConv:
@@ -286,6 +290,26 @@ class FoldedChain:
                                       _nat.ACT_RELU, self.c3.packed6 if x6 else self.c3.packed, self.c3.bias,
                                       self.c3.conv.out_channels, _nat.ACT_RELU, residual=x, out=out)
 
+    def next_applies(self, h, nf: FoldedConv) -> bool:
+        """This chain, on the pre-split operand h, can also run the successor block's conv1 `nf` (1x1 / stride 1 over
+        this block's output, bf16x6, the channel count the kernel is built for)."""
+        c2, c3, n = self.c2.conv, self.c3.conv, nf.conv
+        return (isinstance(h, _nat.Split3) and n.kernel_size == (1, 1) and n.stride == (1, 1) and n.padding == (0, 0)
+                and n.in_channels == c3.out_channels and nf.arith() == "bf16x6"
+                and _nat.chain_conv1_applies(c2.in_channels, c2.out_channels, c2.kernel_size[0], c2.kernel_size[1],
+                                             c2.stride[0], c2.padding[0], c3.out_channels, n.out_channels))
+
+    def call_next(self, h, x, nf: FoldedConv, out=None):
+        """The bf16x6 chain and relu(nf(y)) in one launch -> (y, Split3 of the successor's conv1 output)."""
+        self.prepare(h.device, "bf16x6")
+        nf.prepare(h.device, "bf16x6")
+        c2 = self.c2.conv
+        return _nat.conv2d_chain_conv1_x6(h, self.c2.packed6, self.c2.bias, c2.out_channels, c2.kernel_size[0],
+                                          c2.kernel_size[1], c2.stride[0], c2.padding[0], _nat.ACT_RELU,
+                                          self.c3.packed6, self.c3.bias, self.c3.conv.out_channels, _nat.ACT_RELU,
+                                          nf.packed6, nf.bias, nf.conv.out_channels, _nat.ACT_RELU, residual=x,
+                                          out=out)
+
 
 class FoldedChainTail:
     """Bottleneck conv2/bn2/act2 -> [conv3/bn3 + downsample conv/bn] -> act3 as ONE launch (block 0).
@@ -425,12 +449,15 @@ class ResNet(nn.Module):
         layers = (self.layer1, self.layer2, self.layer3, self.layer4)
         seq = [(li, bi, blk) for li, layer in enumerate(layers, start=1) if li <= max(out_index, 1)
                for bi, blk in enumerate(layer)]
-        for li, bi, blk in seq:
+        h1 = None  # this block's conv1 output, where the preceding block's chain has computed it (CHAIN_CONV1)
+        for i, (li, bi, blk) in enumerate(seq):
             last = li == last_li and bi == len(layers[li - 1]) - 1
-            y = self._block(blk, y, out=out if last else None)
+            ends = li == out_index and bi == len(layers[li - 1]) - 1
+            succ = seq[i + 1][2] if i + 1 < len(seq) and not ends else None
+            y, h1 = self._block(blk, y, out=out if last else None, h1=h1, succ=succ)
             stage += 1
             mark(stage)
-            if li == out_index and bi == len(layers[li - 1]) - 1:
+            if ends:
                 return y
         return y
 
@@ -602,20 +629,35 @@ class ResNet(nn.Module):
         return (self.split_edges and f1.arith() == "bf16x6" and f2.arith() == "bf16x6" and f2.conv.kernel_size[0] > 1
                 and f2.conv.in_channels % 32 == 0 and f1.conv.out_channels % 4 == 0)
 
-    def _block(self, blk, x, out=None):
-        """One residual block of the eval chain."""
+    def _wants_split_conv1(self, blk):
+        """The conv1 of `blk` if the eval chain takes its (ReLU'd) output as a Split3 and nothing else, else None."""
+        kind, fs = self._block_plan(blk)
+        if (kind in ("chain6", "chaintail6") and SPLIT_CHAIN and fs[0].arith() == "bf16x6"
+                and fs[0].conv.out_channels % 32 == 0):
+            return fs[0]
+        return None
+
+    def _block(self, blk, x, out=None, h1=None, succ=None):
+        """One residual block of the eval chain -> (y, h1 of the block `succ` or None).  h1: this block's conv1 output
+        as the preceding block has computed it; succ: the block that follows, whose conv1 a chain6 body runs in its
+        epilogue where it can (CHAIN_CONV1)."""
         kind, fs = self._block_plan(blk)
         if kind in ("chain", "chaintail"):
             h = fs[0](x, relu=True)
-            return fs[1](h, x, out=out)
+            return fs[1](h, x, out=out), None
         if kind in ("chain6", "chaintail6"):
-            split = SPLIT_CHAIN and fs[0].arith() == "bf16x6" and fs[0].conv.out_channels % 32 == 0
-            h = fs[0](x, relu=True, split_out=split)
-            return fs[1](h, x, out=out, arith="bf16x6")
+            if h1 is None:
+                split = SPLIT_CHAIN and fs[0].arith() == "bf16x6" and fs[0].conv.out_channels % 32 == 0
+                h1 = fs[0](x, relu=True, split_out=split)
+            nf = self._wants_split_conv1(succ) if (CHAIN_CONV1 and kind == "chain6" and succ is not None) else None
+            if nf is not None and fs[1].next_applies(h1, nf):
+                return fs[1].call_next(h1, x, nf, out=out)
+            return fs[1](h1, x, out=out, arith="bf16x6"), None
+        assert h1 is None
         if kind == "tail":
             h = fs[0](x, relu=True, split_out=self._split_edge(fs[0], fs[1]))
             h = fs[1](h, relu=True)
-            return fs[2](h, x, out=out)
+            return fs[2](h, x, out=out), None
         sc = fs[0](x, relu=False) if fs[0] is not None else x
         chain = blk.convs()
         fl = fs[1:]
@@ -628,7 +670,7 @@ class ResNet(nn.Module):
             last = idx == len(chain) - 1
             split = not last and self._split_edge(f, fl[idx + 1])
             y = f(y, relu=relu, residual=sc if last else None, out=out if last else None, split_out=split)
-        return y
+        return y, None
 
 
 def resnet18():
